@@ -8,7 +8,19 @@ writing U, V, W (the reference rebuilds its KDTree on every call, interpolator.p
 binning is inside the step).
 
     python bench.py [--gpus N --steps K --warmup W] [--config headline|c2|c3|c4|c5|...]
+    python bench.py --full ...                                 (+ every measurement next to the step)
+    python bench.py --dump-outputs DIR ...                     (+ the last step's outputs as DIR/*.npy)
     torchrun --nproc-per-node N bench.py --gpus N ...          (one process per GPU, RCCL)
+
+A plain run sets up, warms up, times the K steps and prints the line: ``value``, ``ms_per_step``,
+the per-kernel breakdown and the roofline all come from the timed steps' own events.  ``--full``
+adds the measurements that take runs of their own: the CPU baseline (``cpu_baseline``), the
+host-buffer end-to-end leg (``e2e``), the RCCL all-gather reassembly (``allgather_ms``, N > 1) and
+the radius search's mean ball population (c2r's gather model); ``--no-cpu-baseline``, ``--no-e2e``
+and ``--no-allgather`` drop single legs of a ``--full`` run.  ``--dump-outputs DIR`` writes the
+arrays the timed path left after its last step (U, V, W of this rank's slab; the rows' own
+outputs) as ``DIR/<name>.npy`` in float32 / float64, a fixed seeded sample of them when they
+exceed 48 MB in all; the inputs are seeded, so two builds can be compared output for output.
 
 ``--gpus N`` with N > 1 and no torchrun environment starts the N ranks itself: the parent
 process, which has not touched a GPU, runs ``python -m torch.distributed.run --nproc-per-node
@@ -43,7 +55,7 @@ with a plane-index fill in place of the kernel (tests/test_bench_launch.py).
 Rank 0 prints ONE JSON line.  ``roofline.achieved`` = algorithmic bytes of the k-NN kernel
 (SURVEY.md §8(d) gather model, V (6k 8 + 3 s_out) for this rank's slab) / its hipEvent-timed
 average duration; ``roofline.frac_step`` divides the step's bytes (+ 48 B per binned particle)
-by bin + cull + lattice + k-NN time.  ``cpu_baseline`` times the oracle restatement of
+by bin + cull + lattice + k-NN time.  ``cpu_baseline`` (``--full``) times the oracle restatement of
 interpolator.py:126-155 (scipy KDTree + numpy) over z-slabs on a ProcessPoolExecutor — the
 interpolator.py:173-182 / test_parallel.py pattern — on a bounded sample of the same workload,
 with the CPU model and the calibration against the reference (profiles/cpu_calibration_*.json).
@@ -184,7 +196,19 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-allgather", action="store_true", help="N>1: skip the timed RCCL all-gather reassembly")
     ap.add_argument("--no-e2e", action="store_true", help="skip the host-buffer end-to-end interpolate_field timing")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what is measured next to the timed steps: CPU baseline, end-to-end leg, "
+                         "all-gather reassembly, the radius search's ball population")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the last step's outputs as DIR/<name>.npy (float32 / "
+                         "float64; a fixed seeded sample when they exceed 48 MB in all)")
     a = ap.parse_args()
+    if a.steps is not None and a.steps < 1:
+        ap.error("--steps must be >= 1")
+    if a.warmup is not None and a.warmup < 0:
+        ap.error("--warmup must be >= 0")
+    if not a.full:  # a plain run: the timed steps and the line only
+        a.no_cpu_baseline = a.no_e2e = a.no_allgather = True
     cfg = CONFIGS[a.config]
     defaults = dict(grid=cfg["grid"], particles=cfg["particles"], method=cfg["method"], k=cfg["k"],
                     rbf_kernel=cfg.get("rbf_kernel", "thin_plate_spline"), epsilon=cfg.get("epsilon"),
@@ -261,6 +285,35 @@ def lib_sha256():
             return hashlib.sha256(f.read()).hexdigest()[:16]
     except OSError:
         return None
+
+
+DUMP_BUDGET = 48 << 20  # bytes --dump-outputs may write in all
+
+
+def dump_outputs(dirname, arrays, suffix=""):
+    """--dump-outputs: write the device tensors in `arrays` (name -> tensor: what the last timed
+    step left in the step's output buffers) as dirname/<name><suffix>.npy; float32 stays float32,
+    every other dtype is stored as float64 (exact for the byte masks).  When the files would exceed
+    DUMP_BUDGET in all, every array is written as the same fraction of its elements, taken at
+    sorted flat indices from a fixed seed: the same elements in every run and every build."""
+    import torch
+
+    os.makedirs(dirname, exist_ok=True)
+    size = {name: t.numel() * (4 if t.dtype == torch.float32 else 8) for name, t in arrays.items()}
+    total = sum(size.values())
+    picks = {}
+    for name, t in arrays.items():
+        flat = t.reshape(-1)
+        if total > DUMP_BUDGET:
+            m = max(1, int(flat.numel() * (DUMP_BUDGET / total)))
+            key = (flat.numel(), m)
+            if key not in picks:
+                idx = np.sort(np.random.default_rng(20261019).integers(0, flat.numel(), m))
+                picks[key] = torch.from_numpy(idx).to(flat.device)
+            flat = flat[picks[key]]
+        a = flat.cpu().numpy()
+        np.save(os.path.join(dirname, f"{name}{suffix}.npy"),
+                a if a.dtype == np.float32 else a.astype(np.float64))
 
 
 def traffic_from_profiles():
@@ -722,6 +775,12 @@ def main_interp(args):
         elapsed = float(t.item())
     avg = {key: float(np.mean(v)) for key, v in rec.items()}
 
+    if args.dump_outputs:  # this rank's planes of U, V, W (without the divergence's halo planes)
+        dump = {name: o[hlo:hlo + (z1 - z0)] for name, o in zip("UVW", out)}
+        if args.div:
+            dump["div"] = div_out
+        dump_outputs(args.dump_outputs, dump, f"_rank{rank}" if dist is not None else "")
+
     # RCCL all-gather reassembly of the full field, once, reported apart from `value`
     gather_ms = None
     if dist is not None and not args.no_allgather:
@@ -766,9 +825,9 @@ def main_interp(args):
                 "n_rbf_pivoted": int(max(rec["n_rbf_pivoted"])) if rec["n_rbf_pivoted"] else 0}
     else:
         Vk = (zb - za) * G * G  # voxels the k-NN launch computes (slab + redundant halo planes)
-        if radius:  # gather model with the measured mean ball population in place of k
-            k_eff = ball_population(P, ax_h, radius) if P is not None else 0.0
-            alg = int(round(Vk * (6 * k_eff * 8 + 3 * s_out)))
+        ball = ball_population(P, ax_h, radius) if (radius and args.full and P is not None) else None
+        if radius:  # gather model with the measured mean ball population in place of k (--full: 0 without it)
+            alg = int(round(Vk * (6 * (ball or 0.0) * 8 + 3 * s_out)))
         elif args.mask:  # solid voxels are skipped: fluid V in the gather term, + the mask byte
             alg = int(round(Vk * fluid_frac)) * 6 * k * 8 + Vk * (3 * s_out + 1)
         else:
@@ -822,7 +881,8 @@ def main_interp(args):
         if rbf:
             wl += f"; local RBF {kern} k={k} eps={eps} degree={deg} (system {m_sys}) fp64"
         else:
-            wl += ((f"; IDW radius={radius} (mean ball {ball_population(P, ax_h, radius):.2f} particles) p={args.power} fp64"
+            wl += ((f"; IDW radius={radius}" + (f" (mean ball {ball:.2f} particles)" if ball is not None else "") +
+                    f" p={args.power} fp64"
                     if radius else f"; {args.method.upper()} k={k} p={args.power} fp64") +
                    (" (float32 U, V, W)" if out_f32 else "") +
                    (f" + sphere-pack fluid mask ({fluid_frac:.1%} fluid, solid skipped)" if args.mask else "") +
@@ -945,6 +1005,8 @@ def main_div(args):
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"div": out}, f"_rank{rank}" if dist is not None else "")
     vox = G ** 3
     kavg = float(np.mean(k_ms))
     alg = vox * (3 * s + 1 + s)
@@ -1006,6 +1068,8 @@ def main_filter(args):
 
     elapsed, k_ms = _timed(step, args, dist, dev, "ms_knn", ctx)
     st = ctx.last_stats()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"keep": keep, "kth_distance": kth}, f"_rank{rank}" if dist is not None else "")
     kavg = float(np.mean(k_ms))
     # gather model per particle: k+1 neighbour records {x,y,z,u,v,w} + keep byte + k-th distance
     alg = n * ((6 * (k + 1)) * 8 + 1 + 8)
@@ -1090,6 +1154,8 @@ def main_mask(args):
         ms["boundary"].append(e[1].elapsed_time(e[2]))
 
     elapsed, _ = _timed(step_timed, args, dist, dev, None, ctx)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"mask": out, "boundary_xyz": bxyz}, f"_rank{rank}" if dist is not None else "")
     V = G ** 3
     t_s, t_b = float(np.mean(ms["sample"][args.warmup:] or ms["sample"])), float(np.mean(ms["boundary"][args.warmup:] or ms["boundary"]))
     alg_s = 2 * V            # read the raw byte, write the grid byte (same resolution)
@@ -1180,6 +1246,8 @@ def main_linear(args):
 
     elapsed, w_ms = _timed(step, args, dist, dev, "ms_solve", ctx)
     st = ctx.last_stats()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dict(zip("UVW", out)), f"_rank{rank}" if dist is not None else "")
     wavg = float(np.mean(w_ms))
     V = G ** 3
     inside = float((out[0] != 0).double().mean().item())

@@ -11,7 +11,7 @@ run() {  # name, time limit, bench args...  (LINES="a b c" runs only those)
   local name=$1 lim=$2; shift 2
   if [ -n "$LINES" ] && [[ " $LINES " != *" $name "* ]]; then return 0; fi
   echo "== $name: bench.py $*"
-  timeout -k 10 "$lim" python -u bench.py "$@" > "$out/$name.json" 2> "$out/$name.err" || { echo "FAILED $name"; tail -5 "$out/$name.err"; exit 1; }
+  timeout -k 10 "$lim" python -u bench.py --full "$@" > "$out/$name.json" 2> "$out/$name.err" || { echo "FAILED $name"; tail -5 "$out/$name.err"; exit 1; }
   tail -c 400 "$out/$name.json"; echo
   if [ -n "$KT" ]; then  # the same line again under rocprofv3 kernel-trace: its kernels' durations
     export TMPDIR=/tmp
