@@ -719,6 +719,56 @@ __device__ __forceinline__ void insert(double (&bd)[KMAX], int (&bp)[KMAX], doub
     }
 }
 
+// ---- fill-then-sort: the first KMAX candidates of a tile go straight into list positions
+// 0 .. KMAX-1 (no lane's list can be full before then, so no entry is displaced and the threshold
+// stays at the seed bound), and one sorting network then orders the list.  The carry sweep would
+// sort the same entries one at a time at O(KMAX) each. ----
+
+// position `bd`/`bp` of a list being filled takes the candidate (d2, p).  The position still holds
+// its initial value: +inf on an active lane (any finite d2 is below it), -1 on an inactive one
+// (nothing is: the lane keeps -1, as insert() leaves it).  d2 = +inf (no candidate for this lane)
+// leaves the position empty with slot -1.  In place, like insert()'s last slot.
+__device__ __forceinline__ void fill_put(double &bd, int &bp, double d2, int p) {
+    asm("v_cmp_lt_f64 vcc, %[d2], %[bd]\n\t"
+        "v_min_f64 %[bd], %[bd], %[d2]\n\t"
+        "v_cndmask_b32 %[bp], %[bp], %[p], vcc"
+        : [bd] "+v"(bd), [bp] "+v"(bp)
+        : [d2] "v"(d2), [p] "v"(p)
+        : "vcc");
+}
+
+// Sort a filled (or partly filled) pair list ascending in d2.  The list must come out as insert()
+// would have built it, ties included: insert() keeps the earlier arrival first among equal d2, and
+// fill position = arrival order, so the sort has to be STABLE.  Chosen: odd-even transposition
+// (KMAX rounds of adjacent comparators, KMAX (KMAX - 1) / 2 in all: 6 / 28 / 66 at 4 / 8 / 12
+// slots) swapping on strict y < x only; adjacent comparators with a strict test never carry an
+// entry past an equal one.  (Batcher's 19 comparators at 8 slots would need the fill position as
+// a second key: 3-4 more ops each, more in total than the 9 comparators saved.)  Inactive lanes'
+// -1 and empty +inf entries sort as ordinary values (all -1 stays all -1; +inf, slot -1, goes to
+// the end).  One asm block per comparator updates the lower entry in place (the upper goes to
+// fresh registers), 5 VALU like one slot of insert().  Sorting a sorted list changes nothing.
+template <int KMAX>
+__device__ __forceinline__ void sort_pairs(double (&bd)[KMAX], int (&bp)[KMAX]) {
+#pragma unroll
+    for (int r = 0; r < KMAX; ++r) {
+#pragma unroll
+        for (int j = r & 1; j + 1 < KMAX; j += 2) {
+            double hd;
+            int hp;
+            asm("v_cmp_lt_f64 vcc, %[y], %[x]\n\t"
+                "v_max_f64 %[hd], %[x], %[y]\n\t"
+                "v_min_f64 %[x], %[x], %[y]\n\t"
+                "v_cndmask_b32 %[hp], %[py], %[px], vcc\n\t"
+                "v_cndmask_b32 %[px], %[px], %[py], vcc"
+                : [x] "+v"(bd[j]), [px] "+v"(bp[j]), [hd] "=&v"(hd), [hp] "=&v"(hp)
+                : [y] "v"(bd[j + 1]), [py] "v"(bp[j + 1])
+                : "vcc");
+            bd[j + 1] = hd;
+            bp[j + 1] = hp;
+        }
+    }
+}
+
 // min(a, b) for non-NaN operands without fmin's canonicalising v_max
 __device__ __forceinline__ double dmin(double a, double b) { return a < b ? a : b; }
 
@@ -817,6 +867,11 @@ __device__ __forceinline__ void kdist_out(const KnnKernelArgs &a, const double4 
 // the near-tie repair launches use.
 template <int KMAX, bool EXACT>
 constexpr bool kKeyList = KMAX >= 16 && !EXACT;
+
+// whether this instantiation builds its pair list by fill-then-sort (fill_put / sort_pairs; at run
+// time only when k == KMAX).  Key lists, the EXACT repair kernels and radius mode do not.
+template <int KMAX, int MODE, bool EXACT>
+constexpr bool kFillSort = !kKeyList<KMAX, EXACT> && !EXACT && MODE != kModeRadius && KMAX >= 4 && KMAX <= 12;
 
 template <int KMAX, int MODE, bool EXACT>
 constexpr int knn_waves() {
@@ -995,6 +1050,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(knn_waves<K
         else return bd[KMAX - 1];
     };
     double thr = dmin(kth2(), ub2);
+    // fill-then-sort (pair lists with k == KMAX, i.e. no front sentinels): merge iterations run so
+    // far for this tile, across groups, flushes and passes (wave-uniform).  Below KMAX the list is
+    // being filled (positions 0 .. fill-1 written, unsorted unless a partial sort ran); KMAX + 1:
+    // the list is sorted and insert() maintains it (from the start when k < KMAX)
+    constexpr bool FILL = kFillSort<KMAX, MODE, EXACT>;
+    int fill = (FILL && a.kpad == 0) ? 0 : KMAX + 1;
 
     uint32_t n_pass = 0, n_round = 0, n_rows = 0, n_cand = 0, n_acc = 0, n_surv = 0;
 
@@ -1542,6 +1603,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(knn_waves<K
                     if (nit > kTightenMin) {
                         constexpr int KT = KEYS ? KMAX - 2 : KMAX - 1;  // the k-th entry
                         const double ks = KEYS ? a.kscale : 1.0;
+                        if constexpr (FILL) {
+                            if (fill > 0 && fill < KMAX) sort_pairs<KMAX>(bd, bp);  // the network below wants a sorted list
+                        }
                         float sd[KMAX];
 #pragma unroll
                         for (int j = 0; j < KMAX; ++j)
@@ -1596,29 +1660,65 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(knn_waves<K
                         }
                         insert_keys<KMAX, NB>(bd, nk);
                     }
-                } else for (int it = 0; it < nit; ++it) {
-                    // branch-free body (lanes without bits read a valid stale slot and insert inf)
-                    ++n_acc;
-                    const bool has = m != 0ull;
-                    const int lz = __builtin_clzll(m | 1ull);
-                    m &= ~(0x8000000000000000ull >> lz);
-                    const double4 c = gbuf[lz];
-                    const double dx = qx - c.x, dy = qy - c.y, dz = qz - c.z;
-                    const double e2 = (dx * dx + dy * dy) + dz * dz;
-                    if constexpr (MODE == kModeRadius) {
-                        // IDW term of a particle inside the ball (cKDTree's d2 <= r*r test)
-                        if (has && active && e2 <= rad2) {
-                            const double4 val = lds_val[wid][gbuf - buf + lz];
-                            const double w = 1.0 / (np_pow(sqrt_cr(e2), a.power) + a.eps);
-                            rs += w;
-                            rsu += w * val.x;
-                            rsv += w * val.y;
-                            rsw += w * val.z;
+                } else {
+                    int it = 0;
+                    if constexpr (FILL) {
+                        // ---- fill: iteration number `fill` of the tile writes list position `fill`
+                        //      (one peeled copy of the body per position, so the index is a
+                        //      constant; scalar branches on the uniform count).  thr stays: no lane
+                        //      holds KMAX entries yet, so bd[KMAX - 1] is still +inf.  (k-distance
+                        //      mode: a threshold tightened above therefore stays in force for the
+                        //      rest of the fill, where the sweep's update put it back to ub2 after
+                        //      one merge; it bounds the k-th of list and group from above, so the
+                        //      k entries that stay, and their order, are the same.) ----
+                        if (fill < KMAX) {
+#pragma unroll
+                            for (int c = 0; c < KMAX; ++c) {
+                                if (fill == c && it < nit) {
+                                    ++n_acc;
+                                    const bool has = m != 0ull;
+                                    const int lz = __builtin_clzll(m | 1ull);
+                                    m &= ~(0x8000000000000000ull >> lz);
+                                    const double4 c4 = gbuf[lz];
+                                    const double dx = qx - c4.x, dy = qy - c4.y, dz = qz - c4.z;
+                                    const double e2 = (dx * dx + dy * dy) + dz * dz;
+                                    const double d2 = (has && e2 < thr) ? e2 : INFINITY;
+                                    fill_put(bd[c], bp[c], d2, (int)__double_as_longlong(c4.w));
+                                    ++fill;
+                                    ++it;
+                                }
+                            }
+                            if (fill == KMAX) {  // full: sort once, insert() takes over
+                                sort_pairs<KMAX>(bd, bp);
+                                thr = dmin(bd[KMAX - 1], ub2);
+                                fill = KMAX + 1;
+                            }
                         }
-                    } else if constexpr (!KEYS) {
-                        const double d2 = (has && e2 < thr) ? e2 : INFINITY;
-                        insert<KMAX>(bd, bp, d2, (int)__double_as_longlong(c.w));  // no-op where d2 = inf
-                        thr = dmin(bd[KMAX - 1], ub2);
+                    }
+                    for (; it < nit; ++it) {
+                        // branch-free body (lanes without bits read a valid stale slot and insert inf)
+                        ++n_acc;
+                        const bool has = m != 0ull;
+                        const int lz = __builtin_clzll(m | 1ull);
+                        m &= ~(0x8000000000000000ull >> lz);
+                        const double4 c = gbuf[lz];
+                        const double dx = qx - c.x, dy = qy - c.y, dz = qz - c.z;
+                        const double e2 = (dx * dx + dy * dy) + dz * dz;
+                        if constexpr (MODE == kModeRadius) {
+                            // IDW term of a particle inside the ball (cKDTree's d2 <= r*r test)
+                            if (has && active && e2 <= rad2) {
+                                const double4 val = lds_val[wid][gbuf - buf + lz];
+                                const double w = 1.0 / (np_pow(sqrt_cr(e2), a.power) + a.eps);
+                                rs += w;
+                                rsu += w * val.x;
+                                rsv += w * val.y;
+                                rsw += w * val.z;
+                            }
+                        } else if constexpr (!KEYS) {
+                            const double d2 = (has && e2 < thr) ? e2 : INFINITY;
+                            insert<KMAX>(bd, bp, d2, (int)__double_as_longlong(c.w));  // no-op where d2 = inf
+                            thr = dmin(bd[KMAX - 1], ub2);
+                        }
                     }
                 }
                 if constexpr (KEYS) thr = dmin(thr, kth2());  // thresholds only shrink (a tightened one stays)
@@ -1833,6 +1933,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(knn_waves<K
             // ---- exactness: lanes with k-th distance <= R are final ----
             // (key lists: the key bound covers every candidate sharing the k-th key's truncation,
             // so the (k+1)-th slot sees them all too)
+            if constexpr (FILL) {
+                // a partly filled list is sorted before anything reads it (the k-th below, the
+                // epilogue, a split tile's merge); a later pass goes on filling at position `fill`
+                // (the empty entries sort to the end) and the full sort then runs over everything
+                if (fill > 0 && fill < KMAX) sort_pairs<KMAX>(bd, bp);
+            }
             const double worst = uniform(wave_max(kth2()));  // inactive lanes hold -1
             if (MODE == kModeRadius || worst <= R * R || R >= a.rall || nparts > 1) break;
             Rp = R;
