@@ -69,20 +69,14 @@ namespace ptv {
 
 #ifndef PTV_KNN_UNROLL_MAX
 // key-list interpolation epilogues up to this many slots unroll their blocks at compile time;
-// longer lists run the rolled passes.  Round 5: 32 -> 56 (with KEEP below; the key list's 2 x KMAX
-// VGPRs are dead by the epilogue, so the kept distances fit the 2-wave budget: 8 VGPRs spilled at
-// 56 slots).  Same-box A/B, 512^3 / 5M main launch: Sibson k = 45 119.6 -> 87.9 ms, Sibson k = 50
-// 137.2 -> 100.0, IDW k = 36 77.7 -> 75.4, IDW k = 50 101.8 -> 100.8.  At 64 slots Sibson k = 60
-// gains (160.9 -> 126.5) but IDW k = 60 loses (122.1 -> 130.2, 49 VGPRs spilled): 64 stays rolled.
+// longer lists run the rolled passes.  The unrolled ones keep the epilogue's distances (then
+// weights) in registers between passes; the rolled ones re-gather the records every pass (Sibson:
+// four passes).  Round 5: 32 -> 56 (the key list's 2 x KMAX VGPRs are dead by the epilogue, so the
+// kept distances fit the 2-wave budget: 8 VGPRs spilled at 56 slots).  Same-box A/B, 512^3 / 5M
+// main launch: Sibson k = 45 119.6 -> 87.9 ms, Sibson k = 50 137.2 -> 100.0, IDW k = 36 77.7 ->
+// 75.4, IDW k = 50 101.8 -> 100.8.  At 64 slots Sibson k = 60 gains (160.9 -> 126.5) but IDW
+// k = 60 loses (122.1 -> 130.2, 49 VGPRs spilled): 64 stays rolled.
 #define PTV_KNN_UNROLL_MAX 56
-#endif
-#ifndef PTV_VALUE_HALF_BLOCKS
-#define PTV_VALUE_HALF_BLOCKS 1  // dev builds: 0 = the value pass in whole blocks of 8
-#endif
-#ifndef PTV_KNN_KEEP_MAX
-// key lists up to this many slots keep the epilogue's distances (then weights) in registers
-// between passes; longer ones re-gather the records every pass (Sibson: four passes)
-#define PTV_KNN_KEEP_MAX 56
 #endif
 // unroll factors (same-box A/B, 512^3 / 5M, profiles/r06_ab/unroll_ab.txt): the k <= 8 seed
 // network's loop over pairs of seeds by 2 (headline main launch 14.09 -> 13.98 ms; the filter's
@@ -457,65 +451,6 @@ __device__ __forceinline__ double filter_median(const double (&s)[KMAX], int n) 
     else return median_of<KMAX>(s, n);
 }
 
-// numpy's pairwise sum (see pairwise()) fed in index order in blocks of 8 values: block m
-// holds a[m .. m + 7] (entries at or past n ignored).
-struct PairwiseStream {
-    double r[8];
-    double res = 0.0;
-    __device__ __forceinline__ void add(int m, int n, const double (&a)[8]) {
-        if (n < 8) {  // m == 0: sequential from identity 0.0
-            double s = 0.0;
-#pragma unroll
-            for (int i = 0; i < 8; ++i)
-                if (i < n) s += a[i];
-            res = s;
-            return;
-        }
-        const int stop = n - (n & 7);
-        if (m == 0) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) r[i] = a[i];
-        } else if (m < stop) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) r[i] += a[i];
-        } else {  // the tail block (n % 8 entries), after the tree of the accumulators
-            res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-#pragma unroll
-            for (int i = 0; i < 8; ++i)
-                if (m + i < n) res += a[i];
-        }
-    }
-    // the same as add(m, n, a) over the block's half h (entries m + 4h .. m + 4h + 3), both halves in
-    // order: each entry meets the same accumulator or running sum in the same order
-    __device__ __forceinline__ void add4(int m, int h, int n, const double (&a)[4]) {
-        if (n < 8) {
-            double s = h == 0 ? 0.0 : res;
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                if (4 * h + i < n) s += a[i];
-            res = s;
-            return;
-        }
-        const int stop = n - (n & 7);
-        if (m == 0) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) r[4 * h + i] = a[i];
-        } else if (m < stop) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) r[4 * h + i] += a[i];
-        } else {
-            if (h == 0) res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                if (m + 4 * h + i < n) res += a[i];
-        }
-    }
-    __device__ __forceinline__ double finish(int n) {
-        if (n >= 8 && (n & 7) == 0) res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-        return res;
-    }
-};
-
 // numpy pairwise sum of a[0..n) (n <= KMAX <= 128), from identity 0.0.
 template <int KMAX>
 __device__ __forceinline__ double pairwise(const double (&a)[KMAX], int n) {
@@ -859,6 +794,12 @@ __device__ __forceinline__ void kdist_out(const KnnKernelArgs &a, const double4 
         }
     }
 }
+
+}  // namespace ptv
+
+#include "ptv_knn_epilogue.hpp"  // keylist_interp, PairwiseStream (uses the helpers above)
+
+namespace ptv {
 
 // MODE (kModeInterp / kModeKDist / kModeSlots) is a template parameter so that the search-only
 // modes carry no interpolation epilogue: one kernel for every mode put the KMAX = 32 lists at
@@ -2160,633 +2101,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(knn_waves<K
         store_out(a.flags, U, V, W, vo, o[0], o[1], o[2]);
         return;
     }
-    if constexpr (KSL && MODE == kModeInterp && KMAX <= PTV_KNN_UNROLL_MAX) {
-        // up to PTV_KNN_UNROLL_MAX (56) slots: blocks unrolled at compile time (the loads of different
-        // blocks overlap, measured faster than the rolled loop below: Sibson k = 30 79 vs 92 ms at 3
-        // waves per SIMD, Sibson k = 50 100 vs 137 ms at 2)
-        // Key lists (k >= 13): the weights are streamed in blocks of 8 neighbours from the exact
-        // d2, recomputed from the records (the keys hold truncated d2), in the reference's order:
-        // interpolator.py:142-153 (IDW), :102-122 (Sibson).  Register-kept distances where the
-        // list is short enough, record re-gathers otherwise.
-        const int k = a.k;
-        constexpr bool KEEP = KMAX <= PTV_KNN_KEEP_MAX;
-        double dk[KEEP ? KMAX : 1];  // Sibson: d_j, IDW: d2_j
-        auto d2_block = [&](int m, double (&d2)[8]) {
-            double4 rc[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) rc[i] = prec[m + i < k ? slot_at(min(m + i, KMAX - 1)) : slot_at(0)];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) d2[i] = exact_d2(rc[i]);
-        };
-        // u, v, w of 8 value records straight into the product arrays (24 of the 32 bytes: 48
-        // registers in flight, not 64 plus the products)
-        auto val_block = [&](int m, double (&tu)[8], double (&tv)[8], double (&tw)[8]) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const double *r = reinterpret_cast<const double *>(
-                    pval + (m + i < k ? slot_at(min(m + i, KMAX - 1)) : slot_at(0)));
-                const double2 uv = *reinterpret_cast<const double2 *>(r);
-                tu[i] = uv.x;
-                tv[i] = uv.y;
-                tw[i] = r[2];
-            }
-        };
-#if PTV_VALUE_HALF_BLOCKS
-        // the 3-wave lists (KMAX <= 32): blocks in halves (spilled VGPRs at 24 / 32 slots: 30 / 98 ->
-        // 0 / 22; IDW k = 24 46.0 -> 45.0 ms, Sibson k = 30 unchanged); the 2-wave lists keep whole
-        // blocks (IDW / Sibson k = 50 +1.3 / +2.6 % in halves; profiles/r06_ab/value_half_blocks_ab.txt)
-        constexpr bool HALF = KEEP && KMAX <= 32;
-#endif
+    if constexpr (KSL && MODE == kModeInterp) {
+        // key lists (k >= 13): ptv_knn_epilogue.hpp; a tile with an ambiguous or unordered list
+        // goes to the exact repair launch
         double out[3];
-        bool ok = true;
-        double prev = -1.0;
-        if (a.method == PTV_METHOD_SIBSON) {
-            // pass 1: d, 1/(d + eps) -> sum (pairwise), sum d -> mean; the order check
-            PairwiseStream ps_inv, ps_d;
-            double ivmin = INFINITY, dmax = 0.0, dmin_nz = INFINITY;  // operand ranges for div_by below
-#if PTV_VALUE_HALF_BLOCKS
-            if constexpr (HALF) {
-#pragma unroll
-                for (int m = 0; m < KMAX; m += 8) {
-                    if (m < k) {
-#pragma unroll
-                        for (int h = 0; h < 2; ++h) {
-                            double d2[4], dv[4], iv[4];
-                            {
-                                double4 rc[4];
-#pragma unroll
-                                for (int i = 0; i < 4; ++i) {
-                                    const int j = m + 4 * h + i;
-                                    rc[i] = prec[j < k ? slot_at(min(j, KMAX - 1)) : slot_at(0)];
-                                }
-#pragma unroll
-                                for (int i = 0; i < 4; ++i) d2[i] = exact_d2(rc[i]);
-                            }
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) {
-                                const int j = m + 4 * h + i;
-                                dv[i] = sqrt_cr(d2[i]);
-                                iv[i] = 1.0 / (dv[i] + a.eps);
-                                if (j < k) {
-                                    ok = ok && !(d2[i] < prev);
-                                    prev = d2[i];
-                                    ivmin = fmin(ivmin, iv[i]);
-                                    dmax = fmax(dmax, dv[i]);
-                                    if (dv[i] > 0.0) dmin_nz = fmin(dmin_nz, dv[i]);
-                                }
-                                if (j < KMAX) dk[min(j, KMAX - 1)] = dv[i];
-                            }
-                            ps_inv.add4(m, h, k, iv);
-                            ps_d.add4(m, h, k, dv);
-                        }
-                    }
-                }
-            } else
-#endif
-#pragma unroll
-            for (int m = 0; m < KMAX; m += 8) {
-                if (m < k) {
-                    double d2[8], dv[8], iv[8];
-                    d2_block(m, d2);
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) {
-                        dv[i] = sqrt_cr(d2[i]);
-                        iv[i] = 1.0 / (dv[i] + a.eps);
-                        if (m + i < k) {
-                            ok = ok && !(d2[i] < prev);
-                            prev = d2[i];
-                            ivmin = fmin(ivmin, iv[i]);
-                            dmax = fmax(dmax, dv[i]);
-                            if (dv[i] > 0.0) dmin_nz = fmin(dmin_nz, dv[i]);
-                        }
-                        if constexpr (KEEP) {
-                            if (m + i < KMAX) dk[min(m + i, KMAX - 1)] = dv[i];
-                        }
-                    }
-                    ps_inv.add(m, k, iv);
-                    ps_d.add(m, k, dv);
-                }
-            }
-            if (__builtin_amdgcn_ballot_w64(amb || !ok) != 0) {
-                list_tile();
-                return;
-            }
-            const double s_inv = ps_inv.finish(k);
-            const double mean = ps_d.finish(k) / (double)k;
-            auto d_block = [&](int m, double (&dv)[8]) {
-                if constexpr (KEEP) {
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) dv[i] = dk[min(m + i, KMAX - 1)];
-                } else {
-                    double d2[8];
-                    d2_block(m, d2);
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) dv[i] = sqrt_cr(d2[i]);
-                }
-            };
-            // pass 2: std (ddof 0)
-            PairwiseStream ps_var;
-#if PTV_VALUE_HALF_BLOCKS
-            if constexpr (HALF) {
-#pragma unroll
-                for (int m = 0; m < KMAX; m += 8) {
-                    if (m < k) {
-#pragma unroll
-                        for (int h = 0; h < 2; ++h) {
-                            double t[4];
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) {
-                                const double c = dk[min(m + 4 * h + i, KMAX - 1)] - mean;
-                                t[i] = c * c;
-                            }
-                            ps_var.add4(m, h, k, t);
-                        }
-                    }
-                }
-            } else
-#endif
-#pragma unroll
-            for (int m = 0; m < KMAX; m += 8) {
-                if (m < k) {
-                    double dv[8], t[8];
-                    d_block(m, dv);
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) {
-                        const double c = dv[i] - mean;
-                        t[i] = c * c;
-                    }
-                    ps_var.add(m, k, t);
-                }
-            }
-            const double den = sqrt(ps_var.finish(k) / (double)k) + a.eps;
-            // the quotients iv / s_inv and -d / den through one reciprocal each (div_by: correctly
-            // rounded for normal operands and quotients; d = 0 gives 0 exactly) when every lane's
-            // operands are in range, IEEE division otherwise
-            const bool fdiv = __builtin_amdgcn_ballot_w64(!(div_by_ok(ivmin, s_inv, s_inv) && div_by_ok(dmin_nz, dmax, den))) == 0;
-            const double rsi = 1.0 / s_inv, rden = 1.0 / den;
-            auto w_block = [&](int m, double (&w)[8]) {
-                double dv[8];
-                d_block(m, dv);
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    const double iv = 1.0 / (dv[i] + a.eps);
-                    w[i] = fdiv ? div_by(iv, s_inv, rsi) * exp(div_by(-dv[i], den, rden))
-                                : iv / s_inv * exp(-dv[i] / den);
-                }
-            };
-            // pass 3: the exponential weights (kept in place of the distances when the list is
-            // register-held: pass 4 reads them back) and their sum
-            PairwiseStream ps_w;
-            double wmin = INFINITY;
-#if PTV_VALUE_HALF_BLOCKS
-            if constexpr (HALF) {
-#pragma unroll
-                for (int m = 0; m < KMAX; m += 8) {
-                    if (m < k) {
-#pragma unroll
-                        for (int h = 0; h < 2; ++h) {
-                            double w[4];
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) {
-                                const int j = m + 4 * h + i;
-                                const double dv = dk[min(j, KMAX - 1)];
-                                const double iv = 1.0 / (dv + a.eps);
-                                w[i] = fdiv ? div_by(iv, s_inv, rsi) * exp(div_by(-dv, den, rden))
-                                            : iv / s_inv * exp(-dv / den);
-                                if (j < k && w[i] > 0.0) wmin = fmin(wmin, w[i]);  // exp underflow: 0 / s2 exact
-                                if (j < KMAX) dk[min(j, KMAX - 1)] = w[i];
-                            }
-                            ps_w.add4(m, h, k, w);
-                        }
-                    }
-                }
-            } else
-#endif
-#pragma unroll
-            for (int m = 0; m < KMAX; m += 8) {
-                if (m < k) {
-                    double w[8];
-                    w_block(m, w);
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) {
-                        if (m + i < k && w[i] > 0.0) wmin = fmin(wmin, w[i]);  // exp underflow: 0 / s2 exact
-                        if constexpr (KEEP) {
-                            if (m + i < KMAX) dk[min(m + i, KMAX - 1)] = w[i];
-                        }
-                    }
-                    ps_w.add(m, k, w);
-                }
-            }
-            const double s2 = ps_w.finish(k);
-            // w / s2 through one reciprocal when s2, the nonzero w and every quotient are normal
-            const bool fast = __builtin_amdgcn_ballot_w64(!div_by_ok(wmin, s2, s2)) == 0;
-            const double rs2 = 1.0 / s2;
-            // pass 4: normalised weights times the values
-            PairwiseStream pu, pv, pw;
-#if PTV_VALUE_HALF_BLOCKS
-            if constexpr (HALF) {
-#pragma unroll
-                for (int m = 0; m < KMAX; m += 8) {
-                    if (m < k) {
-#pragma unroll
-                        for (int h = 0; h < 2; ++h) {
-                            double tu[4], tv[4], tw4[4];
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) {
-                                const int j = m + 4 * h + i;
-                                const double *r = reinterpret_cast<const double *>(
-                                    pval + (j < k ? slot_at(min(j, KMAX - 1)) : slot_at(0)));
-                                const double2 uv = *reinterpret_cast<const double2 *>(r);
-                                tu[i] = uv.x;
-                                tv[i] = uv.y;
-                                tw4[i] = r[2];
-                            }
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) {
-                                const double w = dk[min(m + 4 * h + i, KMAX - 1)];
-                                const double wn = fast ? div_by(w, s2, rs2) : w / s2;
-                                tu[i] = wn * tu[i];
-                                tv[i] = wn * tv[i];
-                                tw4[i] = wn * tw4[i];
-                            }
-                            pu.add4(m, h, k, tu);
-                            pv.add4(m, h, k, tv);
-                            pw.add4(m, h, k, tw4);
-                        }
-                    }
-                }
-            } else
-#endif
-#pragma unroll
-            for (int m = 0; m < KMAX; m += 8) {
-                if (m < k) {
-                    double w[8], tu[8], tv[8], tw8[8];
-                    val_block(m, tu, tv, tw8);
-                    if constexpr (KEEP) {
-#pragma unroll
-                        for (int i = 0; i < 8; ++i) w[i] = dk[min(m + i, KMAX - 1)];
-                    } else {
-                        w_block(m, w);
-                    }
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) {
-                        const double wn = fast ? div_by(w[i], s2, rs2) : w[i] / s2;
-                        tu[i] = wn * tu[i];
-                        tv[i] = wn * tv[i];
-                        tw8[i] = wn * tw8[i];
-                    }
-                    pu.add(m, k, tu);
-                    pv.add(m, k, tv);
-                    pw.add(m, k, tw8);
-                }
-            }
-            out[0] = pu.finish(k);
-            out[1] = pv.finish(k);
-            out[2] = pw.finish(k);
-        } else {
-            // pass 1: w = 1/(d**p + eps) -> sum (pairwise); the order check
-            PairwiseStream ps;
-            double wmin = INFINITY;
-#if PTV_VALUE_HALF_BLOCKS
-            if constexpr (HALF) {
-#pragma unroll
-                for (int m = 0; m < KMAX; m += 8) {
-                    if (m < k) {
-#pragma unroll
-                        for (int h = 0; h < 2; ++h) {
-                            double d2[4], w[4];
-                            {
-                                double4 rc[4];
-#pragma unroll
-                                for (int i = 0; i < 4; ++i) {
-                                    const int j = m + 4 * h + i;
-                                    rc[i] = prec[j < k ? slot_at(min(j, KMAX - 1)) : slot_at(0)];
-                                }
-#pragma unroll
-                                for (int i = 0; i < 4; ++i) d2[i] = exact_d2(rc[i]);
-                            }
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) {
-                                const int j = m + 4 * h + i;
-                                if (j < k) {
-                                    ok = ok && !(d2[i] < prev);
-                                    prev = d2[i];
-                                }
-                                if (j < KMAX) dk[min(j, KMAX - 1)] = d2[i];
-                                w[i] = 1.0 / (np_pow(sqrt_cr(d2[i]), a.power) + a.eps);
-                                if (j < k) wmin = fmin(wmin, w[i]);
-                            }
-                            ps.add4(m, h, k, w);
-                        }
-                    }
-                }
-            } else
-#endif
-#pragma unroll
-            for (int m = 0; m < KMAX; m += 8) {
-                if (m < k) {
-                    double d2[8], w[8];
-                    d2_block(m, d2);
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) {
-                        if (m + i < k) {
-                            ok = ok && !(d2[i] < prev);
-                            prev = d2[i];
-                        }
-                        if constexpr (KEEP) {
-                            if (m + i < KMAX) dk[min(m + i, KMAX - 1)] = d2[i];
-                        }
-                        w[i] = 1.0 / (np_pow(sqrt_cr(d2[i]), a.power) + a.eps);
-                        if (m + i < k) wmin = fmin(wmin, w[i]);
-                    }
-                    ps.add(m, k, w);
-                }
-            }
-            if (__builtin_amdgcn_ballot_w64(amb || !ok) != 0) {
-                list_tile();
-                return;
-            }
-            const double s = ps.finish(k);
-            // w_j / s through one reciprocal when every quotient is normal (see the k <= 12 path)
-            const bool fast = __builtin_amdgcn_ballot_w64(!div_by_ok(wmin, s, s)) == 0;
-            const double rs = 1.0 / s;
-            // pass 2: normalised weights times the values
-            PairwiseStream pu, pv, pw;
-#if PTV_VALUE_HALF_BLOCKS
-            if constexpr (HALF) {
-#pragma unroll
-                for (int m = 0; m < KMAX; m += 8) {
-                    if (m < k) {
-#pragma unroll
-                        for (int h = 0; h < 2; ++h) {
-                            double tu[4], tv[4], tw4[4];
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) {
-                                const int j = m + 4 * h + i;
-                                const double *r = reinterpret_cast<const double *>(
-                                    pval + (j < k ? slot_at(min(j, KMAX - 1)) : slot_at(0)));
-                                const double2 uv = *reinterpret_cast<const double2 *>(r);
-                                tu[i] = uv.x;
-                                tv[i] = uv.y;
-                                tw4[i] = r[2];
-                            }
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) {
-                                const double d2 = dk[min(m + 4 * h + i, KMAX - 1)];
-                                const double w = 1.0 / (np_pow(sqrt_cr(d2), a.power) + a.eps);
-                                const double wn = fast ? div_by(w, s, rs) : w / s;
-                                tu[i] = wn * tu[i];
-                                tv[i] = wn * tv[i];
-                                tw4[i] = wn * tw4[i];
-                            }
-                            pu.add4(m, h, k, tu);
-                            pv.add4(m, h, k, tv);
-                            pw.add4(m, h, k, tw4);
-                        }
-                    }
-                }
-            } else
-#endif
-#pragma unroll
-            for (int m = 0; m < KMAX; m += 8) {
-                if (m < k) {
-                    double d2[8], tu[8], tv[8], tw8[8];
-                    val_block(m, tu, tv, tw8);
-                    if constexpr (KEEP) {
-#pragma unroll
-                        for (int i = 0; i < 8; ++i) d2[i] = dk[min(m + i, KMAX - 1)];
-                    } else {
-                        d2_block(m, d2);
-                    }
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) {
-                        const double w = 1.0 / (np_pow(sqrt_cr(d2[i]), a.power) + a.eps);
-                        const double wn = fast ? div_by(w, s, rs) : w / s;
-                        tu[i] = wn * tu[i];
-                        tv[i] = wn * tv[i];
-                        tw8[i] = wn * tw8[i];
-                    }
-                    pu.add(m, k, tu);
-                    pv.add(m, k, tv);
-                    pw.add(m, k, tw8);
-                }
-            }
-            out[0] = pu.finish(k);
-            out[1] = pv.finish(k);
-            out[2] = pw.finish(k);
-        }
-        if (a.flags & PTV_FLAG_NAN_TO_NUM) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) out[c] = nan_to_num(out[c]);
-        }
-        store_out(a.flags, U, V, W, vo, out[0], out[1], out[2]);
-        write_stamps();
-        return;
-    } else if constexpr (KSL && MODE == kModeInterp) {
-        // Key lists (k >= 13): the weights are streamed in blocks of 8 neighbours from the exact
-        // d2, recomputed from the records (the keys hold truncated d2), in the reference's order:
-        // interpolator.py:142-153 (IDW), :102-122 (Sibson).  Every pass is a rolled loop over the
-        // blocks (a fully unrolled epilogue was tens of KB of straight-line code per wave): block
-        // b takes slots 0..7 of a copy of the slot list that is rotated down by 8 per block.
-        const int k = a.k;
-        // the slots of block m from the LDS slot list (entries past k: entry 0's, a valid slot)
-        auto rewind = [&]() {};
-        auto next_slots = [&](int m, int (&s8)[8]) {
-            const int s0 = slot_at(0);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) s8[i] = m + i < k ? slot_at(m + i) : s0;
-        };
-        // x, y, z of 8 records (24 of each 32-byte record: 48 VGPRs in flight, not 64)
-        auto xyz_block = [&](const double4 *__restrict__ src, const int (&s8)[8], double (&x)[8], double (&y)[8],
-                             double (&z)[8]) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const double *r = reinterpret_cast<const double *>(src + s8[i]);
-                const double2 xy = *reinterpret_cast<const double2 *>(r);
-                x[i] = xy.x;
-                y[i] = xy.y;
-                z[i] = r[2];
-            }
-        };
-        auto d2_block = [&](const int (&s8)[8], double (&d2)[8]) {
-            double x[8], y[8], z[8];
-            xyz_block(prec, s8, x, y, z);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const double dx = qx - x[i], dy = qy - y[i], dz = qz - z[i];
-                d2[i] = (dx * dx + dy * dy) + dz * dz;
-            }
-        };
-        double out[3];
-        bool ok = true;
-        double prev = -1.0;
-        if (a.method == PTV_METHOD_SIBSON) {
-            // pass 1: d, 1/(d + eps) -> sum (pairwise), sum d -> mean; the order check
-            PairwiseStream ps_inv, ps_d;
-            double ivmin = INFINITY, dmax = 0.0, dmin_nz = INFINITY;  // operand ranges for div_by below
-            rewind();
-#pragma unroll 1
-            for (int m = 0; m < k; m += 8) {
-                int s8[8];
-                next_slots(m, s8);
-                double d2[8], dv[8], iv[8];
-                d2_block(s8, d2);
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    dv[i] = sqrt_cr(d2[i]);
-                    iv[i] = 1.0 / (dv[i] + a.eps);
-                    if (m + i < k) {
-                        ok = ok && !(d2[i] < prev);
-                        prev = d2[i];
-                        ivmin = fmin(ivmin, iv[i]);
-                        dmax = fmax(dmax, dv[i]);
-                        if (dv[i] > 0.0) dmin_nz = fmin(dmin_nz, dv[i]);
-                    }
-                }
-                ps_inv.add(m, k, iv);
-                ps_d.add(m, k, dv);
-            }
-            stamp(t_epi);  // stamp builds: pass 1 of the key-list epilogue
-            if (__builtin_amdgcn_ballot_w64(amb || !ok) != 0) {
-                list_tile();
-                return;
-            }
-            const double s_inv = ps_inv.finish(k);
-            const double mean = ps_d.finish(k) / (double)k;
-            // pass 2: std (ddof 0)
-            PairwiseStream ps_var;
-            rewind();
-#pragma unroll 1
-            for (int m = 0; m < k; m += 8) {
-                int s8[8];
-                next_slots(m, s8);
-                double d2[8], t[8];
-                d2_block(s8, d2);
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    const double c = sqrt_cr(d2[i]) - mean;
-                    t[i] = c * c;
-                }
-                ps_var.add(m, k, t);
-            }
-            const double den = sqrt(ps_var.finish(k) / (double)k) + a.eps;
-            // iv / s_inv and -d / den through one reciprocal each where div_by_ok (the k <= 32 path)
-            const bool fdiv = __builtin_amdgcn_ballot_w64(!(div_by_ok(ivmin, s_inv, s_inv) && div_by_ok(dmin_nz, dmax, den))) == 0;
-            const double rsi = 1.0 / s_inv, rden = 1.0 / den;
-            auto w_of = [&](double d2) {
-                const double d = sqrt_cr(d2);
-                const double iv = 1.0 / (d + a.eps);
-                return fdiv ? div_by(iv, s_inv, rsi) * exp(div_by(-d, den, rden)) : iv / s_inv * exp(-d / den);
-            };
-            // pass 3: the exponential weights' sum
-            PairwiseStream ps_w;
-            double wmin = INFINITY;
-            rewind();
-#pragma unroll 1
-            for (int m = 0; m < k; m += 8) {
-                int s8[8];
-                next_slots(m, s8);
-                double d2[8], w[8];
-                d2_block(s8, d2);
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    w[i] = w_of(d2[i]);
-                    if (m + i < k && w[i] > 0.0) wmin = fmin(wmin, w[i]);
-                }
-                ps_w.add(m, k, w);
-            }
-            const double s2 = ps_w.finish(k);
-            const bool fast = __builtin_amdgcn_ballot_w64(!div_by_ok(wmin, s2, s2)) == 0;
-            const double rs2 = 1.0 / s2;
-            // pass 4: normalised weights times the values
-            PairwiseStream pu, pv, pw;
-            rewind();
-#pragma unroll 1
-            for (int m = 0; m < k; m += 8) {
-                int s8[8];
-                next_slots(m, s8);
-                double d2[8], wn[8];
-                d2_block(s8, d2);
-#pragma unroll
-                for (int i = 0; i < 8; ++i) wn[i] = fast ? div_by(w_of(d2[i]), s2, rs2) : w_of(d2[i]) / s2;
-                double tu[8], tv[8], tw8[8];
-                xyz_block(pval, s8, tu, tv, tw8);
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    tu[i] = wn[i] * tu[i];
-                    tv[i] = wn[i] * tv[i];
-                    tw8[i] = wn[i] * tw8[i];
-                }
-                pu.add(m, k, tu);
-                pv.add(m, k, tv);
-                pw.add(m, k, tw8);
-            }
-            out[0] = pu.finish(k);
-            out[1] = pv.finish(k);
-            out[2] = pw.finish(k);
-        } else {
-            // pass 1: w = 1/(d**p + eps) -> sum (pairwise); the order check
-            auto w_of = [&](double d2) { return 1.0 / (np_pow(sqrt_cr(d2), a.power) + a.eps); };
-            PairwiseStream ps;
-            double wmin = INFINITY;
-            rewind();
-#pragma unroll 1
-            for (int m = 0; m < k; m += 8) {
-                int s8[8];
-                next_slots(m, s8);
-                double d2[8], w[8];
-                d2_block(s8, d2);
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    if (m + i < k) {
-                        ok = ok && !(d2[i] < prev);
-                        prev = d2[i];
-                    }
-                    w[i] = w_of(d2[i]);
-                    if (m + i < k) wmin = fmin(wmin, w[i]);
-                }
-                ps.add(m, k, w);
-            }
-            stamp(t_epi);  // stamp builds: pass 1 of the key-list epilogue
-            if (__builtin_amdgcn_ballot_w64(amb || !ok) != 0) {
-                list_tile();
-                return;
-            }
-            const double s = ps.finish(k);
-            // w_j / s through one reciprocal when every quotient is normal (see the k <= 12 path)
-            const bool fast = __builtin_amdgcn_ballot_w64(!div_by_ok(wmin, s, s)) == 0;
-            const double rs = 1.0 / s;
-            // pass 2: normalised weights times the values
-            PairwiseStream pu, pv, pw;
-            rewind();
-#pragma unroll 1
-            for (int m = 0; m < k; m += 8) {
-                int s8[8];
-                next_slots(m, s8);
-                double d2[8], wn[8];
-                d2_block(s8, d2);
-                if (fast) {
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) wn[i] = div_by(w_of(d2[i]), s, rs);
-                } else {
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) wn[i] = w_of(d2[i]) / s;
-                }
-                double tu[8], tv[8], tw8[8];
-                xyz_block(pval, s8, tu, tv, tw8);
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    tu[i] = wn[i] * tu[i];
-                    tv[i] = wn[i] * tv[i];
-                    tw8[i] = wn[i] * tw8[i];
-                }
-                pu.add(m, k, tu);
-                pv.add(m, k, tv);
-                pw.add(m, k, tw8);
-            }
-            out[0] = pu.finish(k);
-            out[1] = pv.finish(k);
-            out[2] = pw.finish(k);
+        if (!keylist_interp<KMAX>(a, prec, pval, qx, qy, qz, slot_at, amb, out)) {
+            list_tile();
+            return;
         }
         if (a.flags & PTV_FLAG_NAN_TO_NUM) {
 #pragma unroll
