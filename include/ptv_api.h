@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define PTV_API_VERSION 10
+#define PTV_API_VERSION 11
 
 /* error codes */
 #define PTV_OK 0
@@ -275,6 +275,38 @@ typedef struct {
     int chunk_planes;                 /* z planes per nearest-particle + walk chunk (multiple of 4), <= 0: auto */
 } ptv_linear_params;
 
+/*
+ * Projection-method divergence cleaning (physics.clean_divergence_projection, physics.py:149-209;
+ * ABI v11).  Fields and the uint8 fluid mask (nonzero = fluid, required) are float64 / uint8
+ * (nz, ny, nx) C order.  Per outer iteration: the consistent divergence, b = div[fluid] -
+ * mean(div[fluid]), scipy.sparse.linalg.lsqr(A, b, damp, atol, btol, iter_lim) (conlim at scipy's
+ * default 1e8) on the masked 7-point Laplacian of build_laplacian_matrix (physics.py:55-108) applied
+ * matrix-free, and apply_consistent_correction (physics.py:110-147).  The reference passes
+ * iterations = 3, damp = 1e-8, atol = btol = 1e-10, iter_lim = 3000 (physics.py:186).
+ */
+typedef struct {
+    int64_t nx, ny, nz;
+    double dx, dy, dz;
+    const uint8_t *fluid_mask;
+    int iterations;          /* outer iterations, >= 0 */
+    double damp, atol, btol; /* lsqr arguments */
+    int iter_lim;            /* lsqr iteration limit, >= 0 */
+} ptv_clean_params;
+
+#define PTV_CLEAN_MAX_OUTER 16 /* outer iterations with per-solve statistics (later ones still run) */
+typedef struct {
+    int32_t n_outer;   /* solves run */
+    int32_t nan_stop;  /* 1: the last solve returned a NaN and ended the loop (physics.py:189-191) */
+    int64_t n_fluid;   /* fluid voxels (the order of A) */
+    int32_t istop[PTV_CLEAN_MAX_OUTER], itn[PTV_CLEAN_MAX_OUTER]; /* lsqr's istop and itn per solve */
+    double rnorm[PTV_CLEAN_MAX_OUTER];          /* lsqr's r2norm per solve */
+    double mean_abs_div[PTV_CLEAN_MAX_OUTER];   /* mean |div| over fluid before each solve */
+    double ms_iter_median[PTV_CLEAN_MAX_OUTER]; /* median ms per LSQR iteration (over polling batches) */
+    double mean_abs_div_final;
+    double flux_initial, flux_final; /* sum(u[:, :, nx // 2]) * dy * dz (physics.py:160-165) */
+    double ms_total, ms_solve;       /* the call on the device; the LSQR solves alone */
+} ptv_clean_stats;
+
 /* Library / device management. */
 int ptv_version(void);
 /* sizeof(ptv_particles, ptv_grid, ptv_knn_params, ptv_stats, ptv_rbf_params, ptv_div_params):
@@ -284,6 +316,8 @@ int ptv_abi_sizes(int64_t out6[6]);
 int ptv_abi_sizes2(int64_t out3[3]);
 /* sizeof(ptv_linear_params): the same self-check */
 int ptv_abi_sizes3(int64_t out1[1]);
+/* sizeof(ptv_clean_params, ptv_clean_stats): the same self-check */
+int ptv_abi_sizes4(int64_t out2[2]);
 const char *ptv_last_error(void);
 int ptv_device_count(int *out);
 int ptv_init(int device, ptv_ctx **out);
@@ -400,6 +434,37 @@ int ptv_filter_outliers_knn(ptv_ctx *ctx, const ptv_particles *p, const ptv_filt
 /* Same on device pointers, enqueued on `stream` (NULL = the ctx's own stream). */
 int ptv_filter_outliers_knn_dev(ptv_ctx *ctx, const ptv_particles *p, const ptv_filter_params *prm,
                                 uint8_t *keep, double *kth_dist, void *stream, ptv_stats *st);
+
+/*
+ * Divergence cleaning, host buffers: H2D of the fields and mask, the solves on the device, D2H of
+ * the cleaned fields Uo, Vo, Wo (float64 (nz, ny, nx); may be U, V, W themselves).  Replaces
+ * clean_divergence_projection (physics.py:149-209).  Solid voxels of the outputs are 0 once a
+ * correction ran.  A mask without fluid returns PTV_E_ARG.  Results agree with the host solver
+ * normwise, not bit for bit (the norms are summed in another order); two calls on the same input
+ * agree bit for bit.
+ */
+int ptv_clean_divergence(ptv_ctx *ctx, const ptv_clean_params *prm, const double *U, const double *V,
+                         const double *W, double *Uo, double *Vo, double *Wo, ptv_clean_stats *st);
+
+/* Same on device pointers (fields, mask, outputs), enqueued on `stream` (NULL = the ctx's own);
+ * synchronises (the stop flag of each solve is polled, and the statistics are returned). */
+int ptv_clean_divergence_dev(ptv_ctx *ctx, const ptv_clean_params *prm, const double *U, const double *V,
+                             const double *W, double *Uo, double *Vo, double *Wo, void *stream,
+                             ptv_clean_stats *st);
+
+/*
+ * apply_consistent_correction (physics.py:110-147) with phi scattered on the grid (phi_grid,
+ * float64 (nz, ny, nx), 0 at solid voxels), host buffers.  Bit-identical to the reference.
+ * Only nx, ny, nz, dx, dy, dz and fluid_mask of prm are read.
+ */
+int ptv_apply_correction(ptv_ctx *ctx, const ptv_clean_params *prm, const double *U, const double *V,
+                         const double *W, const double *phi_grid, double *Uo, double *Vo, double *Wo);
+
+/*
+ * y = A x for the masked Laplacian of build_laplacian_matrix (physics.py:55-108), x and y on the
+ * grid (float64 (nz, ny, nx); solid entries of x are ignored, of y written as 0), host buffers.
+ */
+int ptv_laplacian_apply(ptv_ctx *ctx, const ptv_clean_params *prm, const double *x_grid, double *y_grid);
 
 /*
  * Last-launch k-NN kernel duration in ms (hipEvent pair recorded around the

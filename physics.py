@@ -8,14 +8,22 @@ names is re-exported; only ``compute_consistent_divergence`` (physics.py:6-53) i
 by the MI355X kernel, also inside the reference module, so that the cleaning loops
 (physics.py:173, :193-194) call the GPU stencil too (bit-identical results).  Without the
 reference module (the GPU box), only the divergence is provided.
+
+Opt-in: with ``PTV_GPU_CLEAN=1`` in the environment, ``clean_divergence_projection`` and
+``apply_consistent_correction`` (physics.py:110-209) are replaced the same way, here and inside the
+reference module, so that the reference's ``clean_divergence`` dispatcher (and ``main.py -d``)
+reaches the GPU solver.  It is not the default because that solver agrees with the host's ``lsqr``
+normwise, not bit for bit (INTEGRATION.md).
 """
 import importlib.util as _ilu
 import os as _os
 import sys as _sys
 
+from ptv_interpolation_amd import physics as _gpu
 from ptv_interpolation_amd.physics import compute_consistent_divergence as _gpu_divergence
 
 compute_consistent_divergence = _gpu_divergence
+_GPU_CLEAN = _os.environ.get("PTV_GPU_CLEAN", "") == "1"
 
 _ROOT = _os.path.dirname(_os.path.abspath(__file__))
 
@@ -46,3 +54,11 @@ if _ref is not None:
     globals().update({k: v for k, v in vars(_ref).items() if not k.startswith("__")})
     _ref.compute_consistent_divergence = _gpu_divergence
     compute_consistent_divergence = _gpu_divergence
+if _GPU_CLEAN:
+    clean_divergence_projection = _gpu.clean_divergence_projection
+    apply_consistent_correction = _gpu.apply_consistent_correction
+    if _ref is not None:
+        _ref.clean_divergence_projection = _gpu.clean_divergence_projection
+        _ref.apply_consistent_correction = _gpu.apply_consistent_correction
+    else:
+        clean_divergence = _gpu.clean_divergence

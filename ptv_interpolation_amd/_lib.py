@@ -97,6 +97,35 @@ class DivParams(C.Structure):
 
 
 _u8p = C.POINTER(C.c_uint8)
+
+
+class CleanParams(C.Structure):
+    _fields_ = [("nx", C.c_int64), ("ny", C.c_int64), ("nz", C.c_int64), ("dx", C.c_double), ("dy", C.c_double),
+                ("dz", C.c_double), ("fluid_mask", _u8p), ("iterations", C.c_int), ("damp", C.c_double),
+                ("atol", C.c_double), ("btol", C.c_double), ("iter_lim", C.c_int)]
+
+
+CLEAN_MAX_OUTER = 16
+
+
+class CleanStats(C.Structure):
+    _fields_ = [("n_outer", C.c_int32), ("nan_stop", C.c_int32), ("n_fluid", C.c_int64),
+                ("istop", C.c_int32 * CLEAN_MAX_OUTER), ("itn", C.c_int32 * CLEAN_MAX_OUTER),
+                ("rnorm", C.c_double * CLEAN_MAX_OUTER), ("mean_abs_div", C.c_double * CLEAN_MAX_OUTER),
+                ("ms_iter_median", C.c_double * CLEAN_MAX_OUTER), ("mean_abs_div_final", C.c_double),
+                ("flux_initial", C.c_double), ("flux_final", C.c_double), ("ms_total", C.c_double),
+                ("ms_solve", C.c_double)]
+
+    def as_dict(self):
+        n = min(self.n_outer, CLEAN_MAX_OUTER)
+        d = {f: getattr(self, f) for f, t in self._fields_ if not hasattr(t, "_length_")}
+        for f in ("istop", "itn", "rnorm", "ms_iter_median"):
+            d[f] = list(getattr(self, f))[:n]
+        # the divergence of the input is measured even when no solve runs (iterations = 0)
+        d["mean_abs_div"] = list(self.mean_abs_div)[:max(n, 1)]
+        return d
+
+
 MASK_BOOL = 0
 MASK_BITS = 1
 
@@ -168,6 +197,13 @@ EXPORTS = {
                                           C.POINTER(Stats)]),
     "ptv_filter_outliers_knn_dev": (C.c_int, [C.c_void_p, C.POINTER(Particles), C.POINTER(FilterParams), _u8p,
                                               _dp, C.c_void_p, C.POINTER(Stats)]),
+    "ptv_abi_sizes4": (C.c_int, [C.POINTER(C.c_int64)]),
+    "ptv_clean_divergence": (C.c_int, [C.c_void_p, C.POINTER(CleanParams), _dp, _dp, _dp, _dp, _dp, _dp,
+                                       C.POINTER(CleanStats)]),
+    "ptv_clean_divergence_dev": (C.c_int, [C.c_void_p, C.POINTER(CleanParams), _dp, _dp, _dp, _dp, _dp, _dp,
+                                           C.c_void_p, C.POINTER(CleanStats)]),
+    "ptv_apply_correction": (C.c_int, [C.c_void_p, C.POINTER(CleanParams), _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "ptv_laplacian_apply": (C.c_int, [C.c_void_p, C.POINTER(CleanParams), _dp, _dp]),
     "ptv_last_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     "ptv_debug_stamps": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double)]),
 }
@@ -256,6 +292,13 @@ def abi_sizes3():
     out = (C.c_int64 * 1)()
     check(lib().ptv_abi_sizes3(out))
     return list(out), [C.sizeof(LinearParams)]
+
+
+def abi_sizes4():
+    """(C sizeof, ctypes sizeof) of ptv_clean_params and ptv_clean_stats."""
+    out = (C.c_int64 * 2)()
+    check(lib().ptv_abi_sizes4(out))
+    return list(out), [C.sizeof(CleanParams), C.sizeof(CleanStats)]
 
 
 class Triangulation:
@@ -739,3 +782,51 @@ class Context:
         check(lib().ptv_divergence_dev(self.h, C.byref(prm), *[C.c_void_p(p) for p in ptrs], C.c_void_p(out_ptr),
                                        C.c_void_p(stream or 0), C.byref(st)))
         return st.as_dict()
+
+    # -- divergence cleaning, projection method (physics.py:55-209) --------
+    @staticmethod
+    def _clean_params(shape, fluid_mask, dx, dy, dz, iterations=0, damp=0.0, atol=0.0, btol=0.0, iter_lim=0):
+        nz, ny, nx = shape
+        mk = np.ascontiguousarray(fluid_mask, dtype=bool).view(np.uint8).reshape(nz, ny, nx)
+        prm = CleanParams(nx, ny, nz, float(dx), float(dy), float(dz), mk.ctypes.data_as(_u8p), int(iterations),
+                          float(damp), float(atol), float(btol), int(iter_lim))
+        return prm, mk  # mk keeps the mask bytes alive for the call
+
+    def clean_divergence(self, u, v, w, fluid_mask, dx, dy, dz, iterations=3, damp=1e-8, atol=1e-10, btol=1e-10,
+                         iter_lim=3000):
+        """Projection-method cleaning of float64 (nz, ny, nx) host fields (physics.py:149-209 with its
+        lsqr arguments as defaults); returns ``((u_c, v_c, w_c), stats dict)``."""
+        f = [np.ascontiguousarray(a, dtype=np.float64) for a in (u, v, w)]
+        prm, _mk = self._clean_params(f[0].shape, fluid_mask, dx, dy, dz, iterations, damp, atol, btol, iter_lim)
+        out = [np.empty_like(a) for a in f]
+        st = CleanStats()
+        check(lib().ptv_clean_divergence(self.h, C.byref(prm), *[as_dp(a) for a in f], *[as_dp(a) for a in out],
+                                         C.byref(st)))
+        return tuple(out), st.as_dict()
+
+    def clean_divergence_dev(self, nx, ny, nz, ptrs, mask_ptr, out_ptrs, dx, dy, dz, iterations=3, damp=1e-8,
+                             atol=1e-10, btol=1e-10, iter_lim=3000, stream=0):
+        """Device-pointer cleaning (float64 fields, uint8 mask and outputs resident in HBM; the outputs
+        may be the inputs); returns the stats dict."""
+        prm = CleanParams(nx, ny, nz, float(dx), float(dy), float(dz), C.cast(C.c_void_p(mask_ptr), _u8p),
+                          int(iterations), float(damp), float(atol), float(btol), int(iter_lim))
+        st = CleanStats()
+        check(lib().ptv_clean_divergence_dev(self.h, C.byref(prm), *[dev_dp(p) for p in ptrs],
+                                             *[dev_dp(p) for p in out_ptrs], C.c_void_p(stream or 0), C.byref(st)))
+        return st.as_dict()
+
+    def apply_correction(self, u, v, w, phi_grid, fluid_mask, dx, dy, dz):
+        """physics.py:110-147 with phi on the grid; float64 (nz, ny, nx) host arrays."""
+        f = [np.ascontiguousarray(a, dtype=np.float64) for a in (u, v, w, phi_grid)]
+        prm, _mk = self._clean_params(f[0].shape, fluid_mask, dx, dy, dz)
+        out = [np.empty_like(a) for a in f[:3]]
+        check(lib().ptv_apply_correction(self.h, C.byref(prm), *[as_dp(a) for a in f], *[as_dp(a) for a in out]))
+        return tuple(out)
+
+    def laplacian_apply(self, x_grid, fluid_mask, dx, dy, dz):
+        """``A @ x`` for the masked Laplacian of physics.py:55-108, x and the result on the grid."""
+        x = np.ascontiguousarray(x_grid, dtype=np.float64)
+        prm, _mk = self._clean_params(x.shape, fluid_mask, dx, dy, dz)
+        y = np.empty_like(x)
+        check(lib().ptv_laplacian_apply(self.h, C.byref(prm), as_dp(x), as_dp(y)))
+        return y

@@ -20,6 +20,7 @@
 
 #include "../../include/ptv_api.h"
 #include "ptv_kernels.hpp"
+#include "ptv_clean.hpp"
 #include "ptv_knn_big.hpp"
 
 namespace ptv {
@@ -100,6 +101,8 @@ struct ptv_ctx {
     DevBuf<int> lin_simp, lin_nbr, lin_v2s, lin_count;           // linear: triangulation (host calls), flags
     DevBuf<double> lin_tr;
     DevBuf<long long> lin_flags;                                 // linear: voxels left to the brute force
+    CleanWork clean;                                             // divergence cleaning: LSQR vectors, state
+    DevBuf<double> clean_fld[4];                                 // its host calls: U, V, W (in place), phi / x
     double *h_bbox = nullptr;  // pinned, 6 doubles
     unsigned long long *h_misc = nullptr;  // pinned scratch words (cull count, halo bound, repair count)
     ptv_stats last{};
@@ -140,6 +143,16 @@ int ptv_abi_sizes3(int64_t out1[1]) {
         return PTV_E_ARG;
     }
     out1[0] = (int64_t)sizeof(ptv_linear_params);
+    return PTV_OK;
+}
+
+int ptv_abi_sizes4(int64_t out2[2]) {
+    if (!out2) {
+        set_error("ptv_abi_sizes4: out is NULL");
+        return PTV_E_ARG;
+    }
+    out2[0] = (int64_t)sizeof(ptv_clean_params);
+    out2[1] = (int64_t)sizeof(ptv_clean_stats);
     return PTV_OK;
 }
 
@@ -238,6 +251,8 @@ int ptv_free(ptv_ctx *c) {
     c->lin_flags.release();
     c->smooth.release();
     for (auto &b : c->fld) b.release();
+    c->clean.release();
+    for (auto &b : c->clean_fld) b.release();
     c->mask_axes.release();
     c->mask_tabs.release();
     c->mask_raw.release();
@@ -1889,6 +1904,119 @@ int ptv_divergence(ptv_ctx *c, const ptv_div_params *prm, const void *U, const v
     c->last.ms_total = tot;
     c->last.n_voxels = nout;
     if (st) *st = c->last;
+    return PTV_OK;
+}
+
+// ---- divergence cleaning (ptv_clean.hip) ----
+static int clean_check(ptv_ctx *c, const ptv_clean_params *prm, CleanGrid &g) {
+    if (!c || !prm) {
+        set_error("NULL context/params");
+        return PTV_E_ARG;
+    }
+    if (!prm->fluid_mask) {
+        set_error("clean: the fluid mask is required");
+        return PTV_E_ARG;
+    }
+    if (prm->nx <= 0 || prm->ny <= 0 || prm->nz <= 0 || prm->nx > (1 << 30) || prm->ny > (1 << 30) ||
+        prm->nz > (1 << 30) || prm->nx * prm->ny * prm->nz > 0x7fff0000LL) {
+        set_error("clean: dimensions must be positive, with fewer than 2^31 voxels");
+        return PTV_E_ARG;
+    }
+    g.nx = (int)prm->nx;
+    g.ny = (int)prm->ny;
+    g.nz = (int)prm->nz;
+    g.dx = prm->dx;
+    g.dy = prm->dy;
+    g.dz = prm->dz;
+    return PTV_OK;
+}
+
+// host fields -> c->clean_fld[0..nf), mask -> c->mask
+static int clean_upload(ptv_ctx *c, const ptv_clean_params *prm, const double *const *src, int nf, hipStream_t s) {
+    const size_t n = (size_t)(prm->nx * prm->ny * prm->nz);
+    for (int i = 0; i < nf; ++i) {
+        PTV_TRY(c->clean_fld[i].ensure(n));
+        PTV_HIP(hipMemcpyAsync(c->clean_fld[i].p, src[i], n * sizeof(double), hipMemcpyHostToDevice, s));
+    }
+    PTV_TRY(c->mask.ensure(n));
+    PTV_HIP(hipMemcpyAsync(c->mask.p, prm->fluid_mask, n, hipMemcpyHostToDevice, s));
+    return PTV_OK;
+}
+
+int ptv_clean_divergence_dev(ptv_ctx *c, const ptv_clean_params *prm, const double *U, const double *V,
+                             const double *W, double *Uo, double *Vo, double *Wo, void *stream,
+                             ptv_clean_stats *st) {
+    CleanGrid g{};
+    PTV_TRY(clean_check(c, prm, g));
+    if (!U || !V || !W || !Uo || !Vo || !Wo) {
+        set_error("clean: NULL field or output");
+        return PTV_E_ARG;
+    }
+    PTV_HIP(hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    const CleanSolve sv{prm->iterations, prm->damp, prm->atol, prm->btol, prm->iter_lim};
+    return clean_run(c->clean, g, sv, prm->fluid_mask, U, V, W, Uo, Vo, Wo, s, st);
+}
+
+int ptv_clean_divergence(ptv_ctx *c, const ptv_clean_params *prm, const double *U, const double *V,
+                         const double *W, double *Uo, double *Vo, double *Wo, ptv_clean_stats *st) {
+    CleanGrid g{};
+    PTV_TRY(clean_check(c, prm, g));
+    if (!U || !V || !W || !Uo || !Vo || !Wo) {
+        set_error("clean: NULL field or output");
+        return PTV_E_ARG;
+    }
+    PTV_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const double *src[3] = {U, V, W};
+    PTV_TRY(clean_upload(c, prm, src, 3, s));
+    const CleanSolve sv{prm->iterations, prm->damp, prm->atol, prm->btol, prm->iter_lim};
+    double *d[3] = {c->clean_fld[0].p, c->clean_fld[1].p, c->clean_fld[2].p};
+    PTV_TRY(clean_run(c->clean, g, sv, c->mask.p, d[0], d[1], d[2], d[0], d[1], d[2], s, st));
+    const size_t nbytes = (size_t)(prm->nx * prm->ny * prm->nz) * sizeof(double);
+    double *dst[3] = {Uo, Vo, Wo};
+    for (int i = 0; i < 3; ++i) PTV_HIP(hipMemcpyAsync(dst[i], d[i], nbytes, hipMemcpyDeviceToHost, s));
+    PTV_HIP(hipStreamSynchronize(s));
+    return PTV_OK;
+}
+
+int ptv_apply_correction(ptv_ctx *c, const ptv_clean_params *prm, const double *U, const double *V,
+                         const double *W, const double *phi_grid, double *Uo, double *Vo, double *Wo) {
+    CleanGrid g{};
+    PTV_TRY(clean_check(c, prm, g));
+    if (!U || !V || !W || !phi_grid || !Uo || !Vo || !Wo) {
+        set_error("apply_correction: NULL field, phi or output");
+        return PTV_E_ARG;
+    }
+    PTV_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const double *src[4] = {U, V, W, phi_grid};
+    PTV_TRY(clean_upload(c, prm, src, 4, s));
+    double *d[3] = {c->clean_fld[0].p, c->clean_fld[1].p, c->clean_fld[2].p};
+    PTV_TRY(launch_clean_correction(g, c->mask.p, d[0], d[1], d[2], c->clean_fld[3].p, d[0], d[1], d[2], s));
+    const size_t nbytes = (size_t)(prm->nx * prm->ny * prm->nz) * sizeof(double);
+    double *dst[3] = {Uo, Vo, Wo};
+    for (int i = 0; i < 3; ++i) PTV_HIP(hipMemcpyAsync(dst[i], d[i], nbytes, hipMemcpyDeviceToHost, s));
+    PTV_HIP(hipStreamSynchronize(s));
+    return PTV_OK;
+}
+
+int ptv_laplacian_apply(ptv_ctx *c, const ptv_clean_params *prm, const double *x_grid, double *y_grid) {
+    CleanGrid g{};
+    PTV_TRY(clean_check(c, prm, g));
+    if (!x_grid || !y_grid) {
+        set_error("laplacian_apply: NULL input or output");
+        return PTV_E_ARG;
+    }
+    PTV_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const double *src[1] = {x_grid};
+    PTV_TRY(clean_upload(c, prm, src, 1, s));
+    const size_t n = (size_t)(prm->nx * prm->ny * prm->nz);
+    PTV_TRY(c->clean_fld[1].ensure(n));
+    PTV_TRY(launch_clean_laplacian(g, c->mask.p, c->clean_fld[0].p, c->clean_fld[1].p, s));
+    PTV_HIP(hipMemcpyAsync(y_grid, c->clean_fld[1].p, n * sizeof(double), hipMemcpyDeviceToHost, s));
+    PTV_HIP(hipStreamSynchronize(s));
     return PTV_OK;
 }
 

@@ -1,0 +1,44 @@
+// ptv_clean.hpp — host interface of the divergence-cleaning solver (ptv_clean.hip).
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <vector>
+
+#include "../../include/ptv_api.h"
+#include "ptv_knn_big.hpp"  // DevBuf
+
+namespace ptv {
+
+struct CleanGrid {
+    int nx, ny, nz;
+    double dx, dy, dz;
+};
+
+// grow-only device scratch of the solver, owned by the context
+struct CleanWork {
+    DevBuf<double> u, v, w, x, div;  // LSQR vectors (dense grids, solid entries 0) and the divergence
+    DevBuf<double> part;             // per-block partial sums (3 rows)
+    DevBuf<double> state, rep;       // LSQR scalar state; report values (flux, mean |div|)
+    double *h_state = nullptr;       // pinned: 2 polling slots + 1 final copy of the state, then rep
+    std::vector<hipEvent_t> ev;      // one per polling batch (+ call start / end)
+    void release();
+};
+
+// LSQR settings of one call (scipy.sparse.linalg.lsqr arguments; conlim is scipy's default 1e8)
+struct CleanSolve {
+    int iterations;
+    double damp, atol, btol;
+    int iter_lim;
+};
+
+// all pointers device memory; Uo, Vo, Wo may alias U, V, W.  Synchronises `s`.
+int clean_run(CleanWork &wk, const CleanGrid &g, const CleanSolve &sv, const uint8_t *M, const double *U,
+              const double *V, const double *W, double *Uo, double *Vo, double *Wo, hipStream_t s,
+              ptv_clean_stats *st);
+int launch_clean_correction(const CleanGrid &g, const uint8_t *M, const double *U, const double *V, const double *W,
+                            const double *phi, double *Uo, double *Vo, double *Wo, hipStream_t s);
+int launch_clean_laplacian(const CleanGrid &g, const uint8_t *M, const double *x, double *y, hipStream_t s);
+
+}  // namespace ptv

@@ -1,4 +1,4 @@
-"""Drop-in for the reference ``physics.compute_consistent_divergence`` (MI355X path).
+"""Drop-in for the reference ``physics`` divergence and projection cleaning (MI355X path).
 
 ``compute_consistent_divergence(u, v, w, mask, dx, dy, dz)`` (physics.py:6-53) is the
 divergence ``view_divergence.py:39,42`` evaluates on the interpolated field and the
@@ -8,8 +8,14 @@ no CPU fallback.  Results are bit-identical to the reference, including numpy's 
 rules: float32 fields with Python-float spacings give float32; a numpy float64 spacing
 (``x[1] - x[0]``, view_divergence.py:22) gives float64 quotients.
 
-The sparse Poisson / variational cleaning solvers (physics.py:55-464) are outside the hot
-path (SURVEY.md §8(f) names only the divergence).
+``clean_divergence_projection`` (physics.py:149-209), the ``--divergence-free`` step of
+main.py, runs on the GPU too: scipy's ``lsqr`` restated matrix-free on the masked 7-point
+Laplacian (csrc/ptv_clean.hip behind ``ptv_clean_divergence``), with the fields resident on the
+device for the whole call.  ``apply_consistent_correction`` (physics.py:110-147) is bit-identical
+to the reference; the solve agrees with the host solver normwise, not bit for bit (its norms are
+summed in another order, and thousands of Lanczos steps amplify the last bit).
+
+``solve_poisson`` and the variational method (physics.py:264-345, :440-514) stay with the reference.
 """
 from __future__ import annotations
 
@@ -17,7 +23,8 @@ import numpy as np
 
 from . import _lib, launcher
 
-__all__ = ["compute_consistent_divergence"]
+__all__ = ["compute_consistent_divergence", "apply_consistent_correction", "clean_divergence_projection",
+           "clean_divergence"]
 
 
 def _result_dtype(ft, h):
@@ -54,3 +61,79 @@ def compute_consistent_divergence(u, v, w, mask, dx, dy, dz):
     return ctx.divergence(u.astype(ft, copy=False), v.astype(ft, copy=False), w.astype(ft, copy=False),
                           np.asarray(mask).astype(bool, copy=False), float(dx), float(dy), float(dz),
                           result_dtype=rt)
+
+
+def _clean_args(u, v, w, mask, iterations=0):
+    """Validation shared by the cleaning entry points, before any device call."""
+    if mask is None:
+        raise ValueError("mask is required (True = fluid)")
+    if not all(isinstance(a, np.ndarray) for a in (u, v, w)):
+        raise NotImplementedError("u, v and w must be numpy arrays (GPU path: float64 (nz, ny, nx))")
+    mask = np.asarray(mask)
+    if not (u.shape == v.shape == w.shape == mask.shape) or u.ndim != 3:
+        raise ValueError(f"u, v, w and mask must share one 3-D shape, got {u.shape}, {v.shape}, "
+                         f"{w.shape}, {mask.shape}")
+    for a in (u, v, w):
+        if a.dtype != np.float64:
+            raise NotImplementedError(f"field dtype {a.dtype} (GPU cleaning path: float64)")
+    if mask.dtype != np.bool_:
+        raise NotImplementedError(f"mask dtype {mask.dtype} (GPU cleaning path: bool, True = fluid)")
+    if int(iterations) != iterations or iterations < 0:
+        raise ValueError(f"iterations must be an integer >= 0, got {iterations!r}")
+    return mask
+
+
+def _ctx():
+    return _lib.Context.get(launcher.devices()[0])
+
+
+def apply_consistent_correction(u, v, w, phi, mask, dx, dy, dz):
+    """physics.py:110-147 on the GPU: ``phi`` is the compact vector over the fluid voxels (C order),
+    as ``lsqr`` returns it.  Bit-identical to the reference."""
+    mask = _clean_args(u, v, w, mask)
+    phi = np.asarray(phi)
+    n_fluid = int(np.count_nonzero(mask))
+    if phi.shape != (n_fluid,):
+        raise ValueError(f"phi must have one entry per fluid voxel ({n_fluid},), got {phi.shape}")
+    if phi.dtype != np.float64:
+        raise NotImplementedError(f"phi dtype {phi.dtype} (GPU cleaning path: float64)")
+    phi_grid = np.zeros_like(u)
+    phi_grid[mask] = phi  # physics.py:116-117
+    return _ctx().apply_correction(u, v, w, phi_grid, mask, float(dx), float(dy), float(dz))
+
+
+def clean_divergence_projection(u, v, w, mask, dx, dy, dz, iterations=3):
+    """physics.py:149-209 on the GPU; prints the reference's report (without scipy's own
+    ``show=True`` iteration log of the first solve) and returns ``(u_c, v_c, w_c)``."""
+    mask = _clean_args(u, v, w, mask, iterations)
+    iterations = int(iterations)
+    (u_c, v_c, w_c), st = _ctx().clean_divergence(u, v, w, mask, float(dx), float(dy), float(dz),
+                                                  iterations=iterations)
+    print(f"Starting Iterative Divergence Cleaning ({iterations} iterations)...")
+    print(f"  [Initial] Net X-Flux (mid-plane): {st['flux_initial']:.4e}")
+    n = st["n_fluid"]
+    for i in range(st["n_outer"]):
+        print(f"\n--- Iteration {i+1}/{iterations} ---")
+        if i < len(st["mean_abs_div"]):
+            print(f"  Current Mean Abs Div: {st['mean_abs_div'][i]:.6e}")
+        print(f"  Solving Poisson (A: {n}x{n})...")
+        if st["nan_stop"] and i == st["n_outer"] - 1:
+            print("  Warning: Solve failed. Stopping iterations.")
+    m_div_init, m_div_final = st["mean_abs_div"][0], st["mean_abs_div_final"]
+    print("\n" + "="*40)
+    print("DIVERGENCE CLEANING COMPLETE")
+    print(f"Initial Mean Abs Div: {m_div_init:.6e}")
+    print(f"Final Mean Abs Div:   {m_div_final:.6e}")
+    print(f"Total Reduction:      {np.float64(m_div_init)/np.float64(m_div_final):.2f}x")
+    print(f"  [Final] Net X-Flux (mid-plane): {st['flux_final']:.4e}")
+    print("="*40 + "\n")
+    clean_divergence_projection.last_stats = st
+    return u_c, v_c, w_c
+
+
+def clean_divergence(u, v, w, mask, dx, dy, dz, iterations=3, method='projection', lambda_reg=1e3):
+    """physics.py:347-354: 'projection' runs on the GPU; the variational method stays with the reference."""
+    if method == 'variational':
+        raise NotImplementedError("method='variational' is not on the GPU path (use the reference's "
+                                  "clean_divergence_variational)")
+    return clean_divergence_projection(u, v, w, mask, dx, dy, dz, iterations=iterations)
