@@ -18,6 +18,9 @@ What it restates (reference = tombultreys/ptv_interpolation, read-only):
 * ``physics.compute_consistent_divergence`` (physics.py:6-53) as
   ``consistent_divergence`` below (an independent per-axis index restatement,
   not the reference's np.roll formulation)
+* ``physics.clean_divergence_projection`` (physics.py:55-209: the masked Laplacian, ``lsqr``, the
+  consistent correction) as ``clean_projection`` below, with the Laplacian both as a CSR matrix
+  and as a matrix-free stencil (two rounding orders whose gap is the cleaning tests' unit)
 * ``interpolator.sample_mask_on_grid`` (interpolator.py:205-238, scipy
   ``RegularGridInterpolator(method='nearest')`` restated as a per-axis interval
   search) and ``interpolator.extract_boundary_particles`` (interpolator.py:240-284,
@@ -544,6 +547,171 @@ def consistent_divergence(u, v, w, mask, dx, dy, dz):
     vfn, vfp = _faces(np.asarray(v), fluid, 1)
     wfn, wfp = _faces(np.asarray(w), fluid, 0)
     return (ufn - ufp) / dx + (vfn - vfp) / dy + (wfn - wfp) / dz
+
+
+# ----------------------------------------------------------------------------
+# projection-method divergence cleaning (physics.py:55-209)
+# ----------------------------------------------------------------------------
+def _face_pairs(fluid, axis):
+    """(lo, hi) slice tuples of the voxels on either side of every interior face along ``axis``
+    and the bool array of faces whose two voxels are both fluid."""
+    lo = [slice(None)] * 3
+    hi = [slice(None)] * 3
+    lo[axis] = slice(0, -1)
+    hi[axis] = slice(1, None)
+    lo, hi = tuple(lo), tuple(hi)
+    return lo, hi, fluid[lo] & fluid[hi]
+
+
+def _inv_h2(dx, dy, dz):
+    """1/h² per array axis (z, y, x), rounded as ``1.0 / (h ** 2)``."""
+    return {2: 1.0 / (dx ** 2), 1: 1.0 / (dy ** 2), 0: 1.0 / (dz ** 2)}
+
+
+def masked_laplacian(mask, dx, dy, dz):
+    """CSR matrix of the 7-point Laplacian over the fluid voxels (compact C-order numbering):
+    ``1/h²`` for every fluid-fluid face pair inside the domain, minus the row's sum on the diagonal
+    (accumulated x-, x+, y-, y+, z-, z+).  A fluid voxel without a fluid face neighbour gives a
+    zero row, an axis of extent 1 no entries."""
+    from scipy import sparse
+
+    fluid = np.asarray(mask).astype(bool)
+    n = int(fluid.sum())
+    number = np.full(fluid.shape, -1, dtype=np.int64)
+    number[fluid] = np.arange(n)
+    h2 = _inv_h2(dx, dy, dz)
+    rows, cols, vals = [], [], []
+    diag = np.zeros(n)
+    for axis in (2, 1, 0):
+        lo, hi, both = _face_pairs(fluid, axis)
+        a, b = number[lo][both], number[hi][both]
+        for r, c in ((b, a), (a, b)):  # the row's lower neighbour, then its upper one
+            rows.append(r)
+            cols.append(c)
+            vals.append(np.full(len(r), h2[axis]))
+            diag -= np.bincount(r, minlength=n) * h2[axis]  # at most one such neighbour per row
+    touched = np.nonzero(diag)[0]
+    rows.append(touched)
+    cols.append(touched)
+    vals.append(diag[touched])
+    A = sparse.coo_matrix((np.concatenate(vals), (np.concatenate(rows), np.concatenate(cols))), shape=(n, n))
+    return A.tocsr()
+
+
+def masked_laplacian_operator(mask, dx, dy, dz):
+    """The operator of ``masked_laplacian`` as a ``LinearOperator`` that applies the stencil with
+    numpy slices, face by face: the same mathematics in a second summation order."""
+    from scipy.sparse.linalg import LinearOperator
+
+    fluid = np.asarray(mask).astype(bool)
+    n = int(fluid.sum())
+    h2 = _inv_h2(dx, dy, dz)
+    faces = [(axis,) + _face_pairs(fluid, axis) for axis in (2, 1, 0)]
+
+    def apply(xc):
+        X = np.zeros(fluid.shape)
+        X[fluid] = np.asarray(xc, dtype=np.float64).ravel()
+        Y = np.zeros(fluid.shape)
+        for axis, lo, hi, both in faces:
+            flow = np.where(both, (X[hi] - X[lo]) * h2[axis], 0.0)
+            Y[lo] += flow
+            Y[hi] -= flow
+        return Y[fluid]
+
+    return LinearOperator((n, n), matvec=apply, rmatvec=apply, dtype=np.float64)
+
+
+def consistent_correction(u, v, w, phi, mask, dx, dy, dz):
+    """Velocity minus the cell-centred gradient of ``phi`` (compact, one entry per fluid voxel).
+    Per axis the face gradient ``(p[i+1] - p[i]) / h`` exists only between two fluid voxels inside
+    the domain; a cell takes the mean ``(g_next + g_prev) / 2.0`` of its two faces; solid voxels of
+    the result are 0.  Elementwise IEEE arithmetic in the reference's order, so bit-identical to it."""
+    fluid = np.asarray(mask).astype(bool)
+    P = np.zeros(fluid.shape)
+    P[fluid] = phi
+    out = []
+    for vel, axis, h in ((u, 2, dx), (v, 1, dy), (w, 0, dz)):
+        lo, hi, both = _face_pairs(fluid, axis)
+        g = np.where(both, (P[hi] - P[lo]) / h, 0.0)
+        g_next = np.zeros(fluid.shape)
+        g_prev = np.zeros(fluid.shape)
+        g_next[lo] = g  # the face above voxel i; none above the last
+        g_prev[hi] = g  # the face below voxel i; none below the first
+        new = np.asarray(vel) - (g_next + g_prev) / 2.0
+        new[~fluid] = 0
+        out.append(new)
+    return tuple(out)
+
+
+def mid_plane_flux(u, dy, dz):
+    """Net x-flux through the middle YZ plane, ``sum(u[:, :, nx // 2]) * dy * dz``."""
+    return float(np.sum(u[:, :, u.shape[2] // 2]) * dy * dz)
+
+
+def clean_projection(u, v, w, mask, dx, dy, dz, iterations=3, damp=1e-8, atol=1e-10, btol=1e-10, iter_lim=3000,
+                     operator=False):
+    """Projection cleaning: per outer iteration the consistent divergence, ``b = div[fluid] -
+    mean(div[fluid])``, ``phi = lsqr(A, b)`` on the masked Laplacian and the consistent correction.
+    ``operator`` picks the matrix-free operator instead of the CSR matrix (another rounding order of
+    the same run).  A solve whose ``phi`` holds a NaN ends the loop, its correction is not applied.
+
+    Returns ``((u_c, v_c, w_c), info)``; ``info`` holds one entry per solve of ``istop``, ``itn``,
+    ``r2norm``, ``anorm``, ``acond``, ``xnorm``, ``phi`` and ``mean_abs_div`` (measured before the
+    solve; with ``iterations=0`` the input's, as the final report needs it), and ``mean_abs_div_final``,
+    ``flux_initial``, ``flux_final``, ``nan_stop``, ``n_outer``, ``n_fluid``."""
+    from scipy.sparse.linalg import lsqr
+
+    fluid = np.asarray(mask).astype(bool)
+    n_fluid = int(fluid.sum())
+    if n_fluid == 0:
+        raise ValueError("the fluid mask has no fluid voxel")
+    cur = [np.array(a, dtype=np.float64) for a in (u, v, w)]
+    info = {k: [] for k in ("istop", "itn", "r2norm", "anorm", "acond", "xnorm", "phi", "mean_abs_div")}
+    info.update(n_fluid=n_fluid, nan_stop=False, n_outer=0, flux_initial=mid_plane_flux(cur[0], dy, dz))
+    A = None
+    with np.errstate(invalid="ignore"):  # NaN inputs are a tested case
+        for _ in range(int(iterations)):
+            if A is None:
+                A = (masked_laplacian_operator if operator else masked_laplacian)(fluid, dx, dy, dz)
+            div = consistent_divergence(*cur, fluid, dx, dy, dz)
+            info["mean_abs_div"].append(float(np.mean(np.abs(div[fluid]))))
+            b = div[fluid]
+            b = b - np.mean(b)
+            res = lsqr(A, b, damp=damp, atol=atol, btol=btol, iter_lim=iter_lim)
+            info["n_outer"] += 1
+            info["istop"].append(int(res[1]))
+            info["itn"].append(int(res[2]))
+            for key, k in (("r2norm", 4), ("anorm", 5), ("acond", 6), ("xnorm", 8)):
+                info[key].append(float(res[k]))
+            info["phi"].append(np.array(res[0]))
+            if np.isnan(res[0]).any():
+                info["nan_stop"] = True
+                break
+            cur = list(consistent_correction(*cur, res[0], fluid, dx, dy, dz))
+        div = consistent_divergence(*cur, fluid, dx, dy, dz)
+        info["mean_abs_div_final"] = float(np.mean(np.abs(div[fluid])))
+        if not info["mean_abs_div"]:
+            info["mean_abs_div"].append(info["mean_abs_div_final"])
+    info["flux_final"] = mid_plane_flux(cur[0], dy, dz)
+    return tuple(cur), info
+
+
+def clean_order_gap(u, v, w, mask, dx, dy, dz, **kw):
+    """``clean_projection`` in both CPU orderings (CSR, then matrix-free).  Returns ``(gap_fields,
+    gap_div, istop_agree, run_csr, run_free)``: the 2-norm of the field difference over all three
+    components relative to the CSR run's, the relative difference of the final mean |div| (both as
+    tests/golden/make_clean_golden.py defines them; 0/0 counts as 0), and whether every solve stopped
+    for the same reason.  Each run is ``(fields, info)``."""
+    run_csr = clean_projection(u, v, w, mask, dx, dy, dz, operator=False, **kw)
+    run_free = clean_projection(u, v, w, mask, dx, dy, dz, operator=True, **kw)
+    a, b = np.stack(run_csr[0]), np.stack(run_free[0])
+    with np.errstate(invalid="ignore"):
+        den = np.linalg.norm(a.ravel())
+        num = np.linalg.norm((a - b).ravel())
+    gap_f = float(num / den) if num != 0 else 0.0
+    m, m2 = run_csr[1]["mean_abs_div_final"], run_free[1]["mean_abs_div_final"]
+    gap_d = float(abs(m - m2) / m) if m != m2 else 0.0
+    return gap_f, gap_d, run_csr[1]["istop"] == run_free[1]["istop"], run_csr, run_free
 
 
 # ----------------------------------------------------------------------------

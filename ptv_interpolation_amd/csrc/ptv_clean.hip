@@ -52,8 +52,9 @@ enum {
 };
 constexpr int kStateLen = 32;
 static_assert(S_COUNT <= kStateLen, "state length");
-// report slots: 0 initial flux, 1 final flux, 2 final mean |div|, 3.. mean |div| before solve i
-constexpr int kRepLen = 3 + PTV_CLEAN_MAX_OUTER;
+// report slots: 0 initial flux, 1 final flux, 2 final mean |div|, 3.. mean |div| before solve i;
+// the last slot takes the solves past PTV_CLEAN_MAX_OUTER, which the stats do not report
+constexpr int kRepLen = 3 + PTV_CLEAN_MAX_OUTER + 1;
 
 enum Phase { PH_DIVSTATS = 0, PH_INIT_BETA, PH_INIT_ALFA, PH_BETA, PH_ALFA, PH_TEST, PH_NAN };
 
@@ -585,8 +586,9 @@ int make_args(const CleanGrid &g, CleanArgs &a) {
         set_error("clean: grids of 2^31 voxels or more are not supported");
         return PTV_E_ARG;
     }
-    if (!(g.dx != 0.0) || !(g.dy != 0.0) || !(g.dz != 0.0)) {
-        set_error("clean: spacings must be non-zero");
+    if (!(g.dx != 0.0) || !(g.dy != 0.0) || !(g.dz != 0.0) || std::isnan(g.dx) || std::isnan(g.dy) ||
+        std::isnan(g.dz)) {
+        set_error("clean: spacings must be non-zero numbers");
         return PTV_E_ARG;
     }
     a.nx = g.nx;
@@ -808,23 +810,23 @@ int clean_run(CleanWork &wk, const CleanGrid &g, const CleanSolve &sv, const uin
     PTV_TRY(sol.event(0));
     PTV_HIP(hipMemsetAsync(wk.state.p, 0, kStateLen * sizeof(double), s));
     PTV_HIP(hipMemsetAsync(wk.rep.p, 0, kRepLen * sizeof(double), s));
-    if (Uo != U) PTV_HIP(hipMemcpyAsync(Uo, U, nbytes, hipMemcpyDeviceToDevice, s));
-    if (Vo != V) PTV_HIP(hipMemcpyAsync(Vo, V, nbytes, hipMemcpyDeviceToDevice, s));
-    if (Wo != W) PTV_HIP(hipMemcpyAsync(Wo, W, nbytes, hipMemcpyDeviceToDevice, s));
-    PTV_TRY(sol.flux(Uo, 0));
+    PTV_TRY(sol.flux(U, 0));
     // the divergence of the input: iteration 1's "current" and the report's "initial" (physics.py:173, :199)
-    PTV_TRY(launch_divergence(d, Uo, Vo, Wo, M, wk.div.p, s));
+    PTV_TRY(launch_divergence(d, U, V, W, M, wk.div.p, s));
     PTV_TRY(sol.div_stats(3));
     PTV_HIP(hipMemcpyAsync(h_final, wk.state.p, kStateLen * sizeof(double), hipMemcpyDeviceToHost, s));
     PTV_HIP(hipStreamSynchronize(s));
     out.n_fluid = (int64_t)h_final[S_NFLUID];
-    if (out.n_fluid <= 0) {
+    if (out.n_fluid <= 0) {  // an argument error: the outputs are not written
         set_error("clean: the fluid mask has no fluid voxel");
         return PTV_E_ARG;
     }
+    if (Uo != U) PTV_HIP(hipMemcpyAsync(Uo, U, nbytes, hipMemcpyDeviceToDevice, s));
+    if (Vo != V) PTV_HIP(hipMemcpyAsync(Vo, V, nbytes, hipMemcpyDeviceToDevice, s));
+    if (Wo != W) PTV_HIP(hipMemcpyAsync(Wo, W, nbytes, hipMemcpyDeviceToDevice, s));
     double ms_solve_total = 0.0;
     for (int i = 0; i < sv.iterations; ++i) {
-        const int slot = std::min(i, PTV_CLEAN_MAX_OUTER - 1);
+        const int slot = std::min(i, PTV_CLEAN_MAX_OUTER);  // past the stats' capacity: the spare slot
         if (i > 0) {
             PTV_TRY(launch_divergence(d, Uo, Vo, Wo, M, wk.div.p, s));
             PTV_TRY(sol.div_stats(3 + slot));

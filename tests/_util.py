@@ -12,6 +12,28 @@ def load(name):
         return {k: f[k] for k in f.files}
 
 
+_clean_fixtures = {}
+
+
+def clean_fixture(name):
+    """A cleaning case's arrays (read-only), merged from clean_<name>.npz and its .p<i>.npz
+    continuation files (tests/golden/make_clean_golden.py)."""
+    if name not in _clean_fixtures:
+        paths = [os.path.join(GOLDEN, f"clean_{name}.npz")] + sorted(glob.glob(os.path.join(GOLDEN, f"clean_{name}.p*.npz")))
+        d = {}
+        for p in paths:
+            with np.load(p, allow_pickle=False) as f:
+                d.update({k: f[k] for k in f.files})
+        for a in d.values():
+            a.setflags(write=False)
+        _clean_fixtures[name] = d
+    return _clean_fixtures[name]
+
+
+def clean_spacings(g):
+    return float(g["dx"]), float(g["dy"]), float(g["dz"])
+
+
 def names(prefixes=("idw", "sibson", "edge", "masked")):
     out = []
     for p in sorted(glob.glob(os.path.join(GOLDEN, "*.npz"))):

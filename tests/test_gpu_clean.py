@@ -10,13 +10,10 @@ reference fixtures of tests/golden/make_clean_golden.py.
   result must lie within 10 x that gap, and stop every solve for the same reason (``istop``).
   The measured ratios are printed (profiles/clean_parity.txt keeps a run's output).
 """
-import glob
-import os
-
 import numpy as np
 import pytest
 
-from tests._util import GOLDEN
+from tests._util import clean_fixture as fixture, clean_spacings as spacings
 
 pytestmark = pytest.mark.gpu
 
@@ -31,27 +28,6 @@ def ctx():
     if _lib.device_count() < 1:
         pytest.fail("no GPU visible: the gpu tests must run on an MI355X")
     return _lib.Context.get(0)
-
-
-_fixtures = {}
-
-
-def fixture(name):
-    """A case's arrays, merged from clean_<name>.npz and its .p<i>.npz continuation files."""
-    if name not in _fixtures:
-        paths = [os.path.join(GOLDEN, f"clean_{name}.npz")] + sorted(glob.glob(os.path.join(GOLDEN, f"clean_{name}.p*.npz")))
-        d = {}
-        for p in paths:
-            with np.load(p, allow_pickle=False) as f:
-                d.update({k: f[k] for k in f.files})
-        for a in d.values():
-            a.setflags(write=False)
-        _fixtures[name] = d
-    return _fixtures[name]
-
-
-def spacings(g):
-    return float(g["dx"]), float(g["dy"]), float(g["dz"])
 
 
 _runs = {}

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from oracle import cpu_ref
-from tests._util import load, names, normwise
+from tests._util import clean_fixture, clean_spacings, load, names, normwise
 
 
 def _bit_exact_expected(g):
@@ -187,3 +187,75 @@ def test_linear_oracle_matches_reference(name):
     out = cpu_ref.linear_grid(g["points"], g["values"], g["ax"], g["ay"], g["az"])
     for a, c in zip(out, "UVW"):
         assert np.array_equal(a, g[c])
+
+
+# ---- divergence cleaning oracle (cpu_ref.clean_projection) against the clean_* fixtures ----
+CLEAN_CASES = ["g12", "g20", "g32", "thin", "iso"]
+
+
+@pytest.mark.parametrize("name", CLEAN_CASES)
+def test_clean_oracle_correction_bit_identical(name):
+    g = clean_fixture(name)
+    out = cpu_ref.consistent_correction(g["u"], g["v"], g["w"], g["phi"], g["mask"], *clean_spacings(g))
+    for a, c in zip(out, "uvw"):
+        assert a.tobytes() == g["corr_" + c].tobytes(), c
+
+
+@pytest.mark.parametrize("name", CLEAN_CASES)
+def test_clean_oracle_laplacian_componentwise_bound(name):
+    """Both forms of the oracle's Laplacian against the reference's CSR product, under the bound
+    the GPU stencil is held to (tests/test_gpu_clean.py): 16 * 2**-53 * (|A| |x|)."""
+    g = clean_fixture(name)
+    m = g["mask"]
+    bound = 16.0 * 2.0 ** -53 * g["lap_abs"][m]
+    A = cpu_ref.masked_laplacian(m, *clean_spacings(g))
+    op = cpu_ref.masked_laplacian_operator(m, *clean_spacings(g))
+    assert A.shape == op.shape == (int(m.sum()),) * 2
+    assert abs(A - A.T).max() == 0
+    for y in (A @ g["lap_x"][m], op.matvec(g["lap_x"][m])):
+        assert (np.abs(y - g["lap_y"][m]) <= bound).all()
+    if name == "iso":  # the enclosed fluid voxel is a zero row
+        assert (np.diff(A.indptr) == 0).sum() >= 1
+
+
+@pytest.mark.parametrize("its", [1, 3])
+@pytest.mark.parametrize("name", ["g12", "thin", "iso"])
+def test_clean_oracle_within_the_fixture_order_gap(name, its):
+    """The oracle's CSR run against the reference's: same istop per solve, fields and mean |div|
+    within 10 x the fixture's own order gap.  g20 and g32 take tens of seconds on a CPU and are not
+    in the suite; run once by hand (ratio to the gap, fields / mean |div|):
+      g20 its=1 0.000 / 0.000, its=3 0.000 / 0.000, istop [1, 1, 1], itn [2550, 2606, 2653]
+      g32 its=1 0.000 / 0.000, its=3 0.000 / 0.000, istop [7, 7, 7]
+    (the oracle's CSR matrix holds the reference's entries in the reference's order, so the runs
+    coincide to the bit)."""
+    g = clean_fixture(name)
+    (u, v, w), info = cpu_ref.clean_projection(g["u"], g["v"], g["w"], g["mask"], *clean_spacings(g), iterations=its)
+    ref = np.stack([g[f"{c}_it{its}"] for c in "uvw"])
+    k = 0 if its == 1 else 1
+    gap_f, gap_d = float(g["order_gap_fields"][k]), float(g["order_gap_div"][k])
+    diff_f = float(np.linalg.norm((np.stack([u, v, w]) - ref).ravel()) / np.linalg.norm(ref.ravel()))
+    mdiv = float(g[f"mean_abs_div_it{its}"])
+    diff_d = abs(info["mean_abs_div_final"] - mdiv) / mdiv
+    print(f"clean oracle {name} iterations={its}: fields {diff_f:.3e} / gap {gap_f:.3e}; mean|div| {diff_d:.3e} / "
+          f"gap {gap_d:.3e}; istop {info['istop']} itn {info['itn']} (reference {g[f'itn_it{its}'].tolist()})")
+    assert info["istop"] == g[f"istop_it{its}"].tolist()
+    assert info["n_outer"] == its and not info["nan_stop"] and info["n_fluid"] == int(g["mask"].sum())
+    assert diff_f <= 10.0 * gap_f
+    assert diff_d <= 10.0 * gap_d
+
+
+def test_clean_oracle_order_gap_and_edges():
+    """clean_order_gap restates the fixture's own gap definition; iterations=0 returns copies."""
+    g = clean_fixture("iso")
+    args = (g["u"], g["v"], g["w"], g["mask"], *clean_spacings(g))
+    gap_f, gap_d, agree, (f_csr, i_csr), (f_free, i_free) = cpu_ref.clean_order_gap(*args, iterations=1)
+    assert agree and i_csr["istop"] == g["istop_it1"].tolist()
+    # the fixture's gap came from the same two orderings of the reference; same order of magnitude
+    assert 0.1 * float(g["order_gap_fields"][0]) <= gap_f <= 10.0 * float(g["order_gap_fields"][0])
+    assert gap_d <= 10.0 * float(g["order_gap_div"][0])
+    (u, v, w), info = cpu_ref.clean_projection(*args, iterations=0)
+    for a, c in zip((u, v, w), "uvw"):
+        assert a.tobytes() == g[c].tobytes() and a is not g[c]
+    assert info["n_outer"] == 0 and info["istop"] == [] and info["mean_abs_div"] == [info["mean_abs_div_final"]]
+    with pytest.raises(ValueError):
+        cpu_ref.clean_projection(g["u"], g["v"], g["w"], np.zeros_like(g["mask"]), *clean_spacings(g))
