@@ -514,6 +514,21 @@ int prepare(ptv_ctx *c, const ptv_particles *p, const ptv_grid *g, const SearchP
         }
     }
 
+    // squared distances must neither overflow nor lose bits to underflow in float64 (the tested range
+    // is 2^-80 .. 2^80 of unit coordinates)
+    {
+        double maxabs = 0.0, maxext = 0.0;
+        for (int a = 0; a < 3; ++a) {
+            maxabs = std::max(maxabs, std::max(std::fabs(lo[a]), std::fabs(hi[a])));
+            maxext = std::max(maxext, hi[a] - lo[a]);
+        }
+        if (maxabs > 0x1p500 || (maxext > 0.0 && maxext < 0x1p-500)) {
+            set_error("coordinates outside the supported range: |coordinate| <= 2^500 and a bounding box of "
+                      "extent 0 or >= 2^-500");
+            return PTV_E_UNSUPPORTED;
+        }
+    }
+
     // 2. binning
     const bool small_k = kmax_for(prm->k) <= 8;
     const bool seeded_lattice = sep && prm->lattice_bounds >= 0;  // union seeds bound the large-k search
@@ -845,13 +860,15 @@ int run_knn_auto(ptv_ctx *c, const ptv_particles *p, const ptv_grid *g, const pt
             used.bot = c->cmap[1].p;
             uint32_t *h_total = reinterpret_cast<uint32_t *>(c->h_misc);
             PTV_HIP(hipEventRecord(c->ev_cull0, s));
+            if (spec) {  // the gate: a kept particle with a non-finite coordinate fails it too (no box is reduced)
+                PTV_TRY(c->halo_need.ensure(1));
+                PTV_HIP(hipMemsetAsync(c->halo_need.p, 0, sizeof(unsigned long long), s));
+            }
             PTV_TRY(launch_cull(src, n, az, (int)g->z_begin, (int)g->z_end, 0.0, c->cull_win.p, c->cull_cnt.p,
-                                c->cull_mask.p, dst, nullptr, s, &used));
+                                c->cull_mask.p, dst, nullptr, s, &used, spec ? c->halo_need.p : nullptr));
             if (spec) {
                 // the cached kept count and bounding box (the same particles give the same), checked on
                 // the device: a mismatch fails the gate and the call reruns with every particle binned
-                PTV_TRY(c->halo_need.ensure(1));
-                PTV_HIP(hipMemsetAsync(c->halo_need.p, 0, sizeof(unsigned long long), s));
                 PTV_TRY(launch_key_check(c->cfp.p, c->ckey_dev.p, (int)nkey, c->cull_cnt.p + nb, (uint32_t)c->ckept,
                                          c->halo_need.p, s));
                 PTV_HIP(hipEventRecord(c->ev_cull1, s));

@@ -40,6 +40,8 @@ struct BBoxArgs {
     const uint32_t *dn;  // particle count on the device (the slab cull's), or NULL: n
 };
 
+// A non-finite coordinate (NaN, +-inf) makes its axis' upper bound +inf, which the host's finiteness
+// test of the box rejects (a NaN particle must never reach cell_coord's (int) conversion).
 __global__ __launch_bounds__(256) void k_bbox(BBoxArgs a, double *partials) {
     double lo[3], hi[3];
 #pragma unroll
@@ -54,6 +56,7 @@ __global__ __launch_bounds__(256) void k_bbox(BBoxArgs a, double *partials) {
 #pragma unroll
         for (int d = 0; d < 3; ++d) {
             double v = a.p[d][i];
+            if (!(v - v == 0.0)) v = INFINITY;  // NaN or +-inf: fmin / fmax would drop a NaN
             lo[d] = fmin(lo[d], v);
             hi[d] = fmax(hi[d], v);
         }
@@ -62,6 +65,7 @@ __global__ __launch_bounds__(256) void k_bbox(BBoxArgs a, double *partials) {
     for (int d = 0; d < 3; ++d) {
         for (int64_t i = t0; i < a.qn[d]; i += stride) {
             double v = a.q[d][i];
+            if (!(v - v == 0.0)) v = INFINITY;
             lo[d] = fmin(lo[d], v);
             hi[d] = fmax(hi[d], v);
         }
@@ -139,7 +143,8 @@ int launch_bbox(const double *const px[3], int64_t n, const double *const qa[3],
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ int cell_coord(double v, double o, double ic, int nc) {
     double f = floor((v - o) * ic);
-    int c = (f < 0.0) ? 0 : (f >= (double)nc ? nc - 1 : (int)f);
+    // (!(f >= 0): a NaN takes cell 0 too; the speculative slab cull bins before its gate is read)
+    int c = !(f >= 0.0) ? 0 : (f >= (double)nc ? nc - 1 : (int)f);
     return c;
 }
 
@@ -377,11 +382,15 @@ __device__ __forceinline__ bool cull_keep(const double *__restrict__ x, const do
                                           const CullMap &m) {
     const double v = z[i];
     if (v >= lo && v <= hi) return true;
+    // a non-finite coordinate (NaN, +-inf) is always kept: the bounding box of the kept set (or, on
+    // the speculative path, k_cull_write's flag) then rejects the call, as it would without the cull
+    const double px = x[i], py = y[i];
+    if (!((v - v) + (px - px) + (py - py) == 0.0)) return true;
     if (m.top == nullptr) return false;
     const int cx = (int)fmin(fmax(floor((x[i] - m.x0) * m.icw), 0.0), (double)(m.mx - 1));
     const int cy = (int)fmin(fmax(floor((y[i] - m.y0) * m.ich), 0.0), (double)(m.my - 1));
     const int c = cy * m.mx + cx;
-    return v > hi ? v <= m.top[c] : v >= m.bot[c];  // NaN coordinates: never kept
+    return v > hi ? v <= m.top[c] : v >= m.bot[c];
 }
 
 // pass 1: the keep test of every particle, one ballot mask per (block item, wave) and the block's count
@@ -416,7 +425,8 @@ struct Cols6 {
 // Item (j, thread) of a block is particle base + j*256 + thread: j-major, thread-minor is index
 // order, so the ranks below preserve it
 __global__ __launch_bounds__(256) void k_cull_write(Cols6 c, int64_t n, const unsigned long long *__restrict__ masks,
-                                                    const uint32_t *__restrict__ boff) {
+                                                    const uint32_t *__restrict__ boff,
+                                                    unsigned long long *__restrict__ fail) {
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const int64_t base = (int64_t)blockIdx.x * kCullTile + threadIdx.x;
     const unsigned long long *bm = masks + (size_t)blockIdx.x * kCullItems * 4;
@@ -434,6 +444,11 @@ __global__ __launch_bounds__(256) void k_cull_write(Cols6 c, int64_t n, const un
             const int64_t i = base + (int64_t)j * 256;
 #pragma unroll
             for (int a = 0; a < 6; ++a) c.dst[a][r] = c.src[a][i];
+            if (fail != nullptr) {  // a kept particle with a non-finite coordinate fails the caller's gate
+                const double px = c.src[0][i], py = c.src[1][i], pz = c.src[2][i];
+                if (!((px - px) + (py - py) + (pz - pz) == 0.0))
+                    atomicMax(fail, (unsigned long long)__double_as_longlong(INFINITY));
+            }
         }
         off += (uint32_t)(__builtin_popcountll(w0) + __builtin_popcountll(w1) + __builtin_popcountll(w2) +
                           __builtin_popcountll(w3));
@@ -447,7 +462,7 @@ size_t cull_mask_words(int64_t n) { return cull_blocks(n) * kCullItems * 4; }
 
 int launch_cull(const double *const src[6], int64_t n, const double *az, int z0, int z1, double halo, double *win,
                 uint32_t *bcount, unsigned long long *masks, double *const dst[6], uint32_t *h_total, hipStream_t s,
-                const CullMap *map) {
+                const CullMap *map, unsigned long long *fail) {
     const int nb = (int)cull_blocks(n);
     const CullMap m = map != nullptr ? *map : CullMap{};
     hipLaunchKernelGGL(k_slab_window, dim3(1), dim3(256), 0, s, az, z0, z1, map != nullptr ? 0.0 : halo, win);
@@ -460,7 +475,7 @@ int launch_cull(const double *const src[6], int64_t n, const double *az, int z0,
         c.dst[a] = dst[a];
     }
     hipLaunchKernelGGL(k_cull_write, dim3(nb), dim3(256), 0, s, c, n, (const unsigned long long *)masks,
-                       (const uint32_t *)bcount);
+                       (const uint32_t *)bcount, fail);
     PTV_HIP(hipGetLastError());
     if (h_total != nullptr) PTV_HIP(hipMemcpyAsync(h_total, bcount + nb, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     return PTV_OK;

@@ -47,7 +47,7 @@ struct CullMap {
 size_t cull_mask_words(int64_t n);
 int launch_cull(const double *const src[6], int64_t n, const double *az, int z0, int z1, double halo, double *win,
                 uint32_t *bcount, unsigned long long *masks, double *const dst[6], uint32_t *h_total, hipStream_t s,
-                const CullMap *map = nullptr);
+                const CullMap *map = nullptr, unsigned long long *fail = nullptr);
 // the map a slab needs, from its finest lattice (axes lax / lay / laz, n[3] points, k-th distance
 // bounds dk over the particles binned): top / bot per cell of m's geometry; cols: 7 (n0-1)(n1-1)
 // doubles and keys: 2 mx my u64 of scratch; every cell reach U is widened by the relative `slack`.
