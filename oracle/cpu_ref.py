@@ -463,7 +463,7 @@ def linear_grid(points, values, ax, ay, az, fill_value=0.0, z0=0, z1=None):
 
 
 def lattice_axis(a, step=4):
-    """The library's coarse-lattice axis (ptv_api.cpp prepare / k_subsample): every `step`-th
+    """The library's coarse-lattice axis (ptv_search.cpp build_lattice / k_subsample): every `step`-th
     value of `a` plus the last."""
     a = np.asarray(a, dtype=np.float64)
     n = len(a)

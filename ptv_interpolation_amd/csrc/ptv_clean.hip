@@ -654,13 +654,8 @@ struct Solver {
         return PTV_OK;
     }
     int event(size_t k) {
-        while (wk.ev.size() <= k) {
-            hipEvent_t e = nullptr;
-            PTV_HIP(hipEventCreate(&e));
-            wk.ev.push_back(e);
-        }
-        PTV_HIP(hipEventRecord(wk.ev[k], s));
-        return PTV_OK;
+        if (wk.ev.size() <= k) wk.ev.resize(k + 1);
+        return wk.ev[k].record(s);
     }
 
     // events 2 .. 2 + batches bracket the polling batches; returns the median ms per iteration
@@ -693,11 +688,11 @@ struct Solver {
                 PTV_TRY(scalar(PH_TEST));
             }
             batch_iters.push_back(cnt);
-            PTV_HIP(hipMemcpyAsync(wk.h_state + (batches & 1) * kStateLen, wk.state.p, sbytes, hipMemcpyDeviceToHost, s));
+            PTV_HIP(hipMemcpyAsync(wk.h_state.p + (batches & 1) * kStateLen, wk.state.p, sbytes, hipMemcpyDeviceToHost, s));
             PTV_TRY(event(4 + batches));
             if (batches >= 1) {  // poll one batch behind the enqueue: the device never waits for the host
                 PTV_HIP(hipEventSynchronize(wk.ev[4 + batches - 1]));
-                stopped = wk.h_state[((batches - 1) & 1) * kStateLen + S_STOP] != 0.0;
+                stopped = wk.h_state.p[((batches - 1) & 1) * kStateLen + S_STOP] != 0.0;
             }
         }
         if (vec2) hipLaunchKernelGGL(k_nan<2>, dim3(nb), dim3(kThreads), 0, s, a, wk.x.p, wk.part.p);
@@ -736,21 +731,6 @@ bool all_aligned16(P... p) {
 }
 
 }  // namespace
-
-void CleanWork::release() {
-    u.release();
-    v.release();
-    w.release();
-    x.release();
-    div.release();
-    part.release();
-    state.release();
-    rep.release();
-    if (h_state) (void)hipHostFree(h_state);
-    h_state = nullptr;
-    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-    ev.clear();
-}
 
 int launch_clean_laplacian(const CleanGrid &g, const uint8_t *M, const double *x, double *y, hipStream_t s) {
     CleanArgs a{};
@@ -791,8 +771,8 @@ int clean_run(CleanWork &wk, const CleanGrid &g, const CleanSolve &sv, const uin
     PTV_TRY(wk.part.ensure(3 * (size_t)nb));
     PTV_TRY(wk.state.ensure(kStateLen));
     PTV_TRY(wk.rep.ensure(kRepLen));
-    if (!wk.h_state) PTV_HIP(hipHostMalloc(&wk.h_state, (3 * kStateLen + kRepLen) * sizeof(double)));
-    double *h_final = wk.h_state + 2 * kStateLen, *h_rep = wk.h_state + 3 * kStateLen;
+    PTV_TRY(wk.h_state.ensure(3 * kStateLen + kRepLen));
+    double *h_final = wk.h_state.p + 2 * kStateLen, *h_rep = wk.h_state.p + 3 * kStateLen;
 
     Solver sol{wk, a, LsqrCfg{sv.damp, sv.atol, sv.btol, 1.0 / 1e8, sv.iter_lim}, M, s, vec2, nb};
     DivArgs d{};

@@ -7,7 +7,7 @@
 #include <vector>
 
 #include "../../include/ptv_api.h"
-#include "ptv_knn_big.hpp"  // DevBuf
+#include "ptv_own.hpp"
 
 namespace ptv {
 
@@ -21,9 +21,8 @@ struct CleanWork {
     DevBuf<double> u, v, w, x, div;  // LSQR vectors (dense grids, solid entries 0) and the divergence
     DevBuf<double> part;             // per-block partial sums (3 rows)
     DevBuf<double> state, rep;       // LSQR scalar state; report values (flux, mean |div|)
-    double *h_state = nullptr;       // pinned: 2 polling slots + 1 final copy of the state, then rep
-    std::vector<hipEvent_t> ev;      // one per polling batch (+ call start / end)
-    void release();
+    PinnedBuf<double> h_state;       // pinned: 2 polling slots + 1 final copy of the state, then rep
+    std::vector<Event> ev;           // one per polling batch (+ call start / end)
 };
 
 // LSQR settings of one call (scipy.sparse.linalg.lsqr arguments; conlim is scipy's default 1e8)

@@ -1,42 +1,12 @@
-// ptv_knn_big.hpp — grow-only device buffers, and the large-k k-NN path (ptv_knn_big.hip).
+// ptv_knn_big.hpp — the large-k k-NN path (ptv_knn_big.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <string>
-
 #include "../../include/ptv_api.h"
-#include "ptv_common.hpp"
+#include "ptv_own.hpp"
 
 namespace ptv {
-
-// a grow-only device buffer (contents are not kept across a growth)
-template <typename T>
-struct DevBuf {
-    T *p = nullptr;
-    size_t cap = 0;  // elements
-    int ensure(size_t n) {
-        if (n <= cap && p) return PTV_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        size_t want = std::max<size_t>(n, 1);
-        hipError_t e = hipMalloc(&p, want * sizeof(T));
-        if (e != hipSuccess) {
-            p = nullptr;
-            set_error("hipMalloc of " + std::to_string(want * sizeof(T)) + " bytes failed: " + hipGetErrorString(e));
-            return PTV_E_NOMEM;
-        }
-        cap = want;
-        return PTV_OK;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
 
 // queries of the large-k path: voxels [z0 plane ...) of a grid (separable axes or point lists, an
 // optional fluid mask), or (particles = 1) the particles themselves in original order (the filter)
@@ -68,11 +38,6 @@ struct BigScratch {
     DevBuf<unsigned long long> ub, incl, temp, keys, keys2, fa, fa2, fb;
     DevBuf<uint32_t> vals, vals2;
     DevBuf<int> seg_b, seg_e, fseg;
-    void release() {
-        R.release(); fmed.release(); ub.release(); incl.release(); temp.release(); keys.release();
-        keys2.release(); fa.release(); fa2.release(); fb.release(); vals.release(); vals2.release();
-        seg_b.release(); seg_e.release(); fseg.release();
-    }
 };
 
 // candidate entries per sub-chunk (a (d2, slot) pair and its sorted copy: 24 B each)

@@ -60,7 +60,7 @@ struct NsBuild {
     }
 };
 
-// _monomial_powers(3, degree) (_rbfinterp.py:48-79; monomial_powers in ptv_api.cpp) packed px | py
+// _monomial_powers(3, degree) (_rbfinterp.py:48-79; monomial_powers in ptv_run_chunked.cpp) packed px | py
 // << 8 | pz << 16: degree 0 is the first entry, degree 1 the first 4, degree 2 all 10 (the order is
 // by degree, so NP alone fixes every exponent)
 constexpr int kNsPow[10] = {0, 1, 256, 65536, 2, 1 | 256, 1 | 65536, 512, 256 | 65536, 131072};

@@ -46,7 +46,7 @@ def test_case_shapes():
 
 def test_dense_grid_builds_the_lattice():
     """The lattice-sized grid and its slab are above the library's 50 000-voxel lattice threshold
-    (ptv_api.cpp kLatticeStopPoints) with every extent >= 9; the small grid is not."""
+    (ptv_search.cpp kLatticeStopPoints) with every extent >= 9; the small grid is not."""
     nx, ny, nz = G.DENSE
     z0, z1 = G.DENSE_SLAB
     assert nx * ny * (z1 - z0) > 50000 and min(nx, ny, z1 - z0) >= 9 and 0 < z0 < z1 < nz
