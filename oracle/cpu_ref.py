@@ -125,10 +125,11 @@ def knn_kdtree(points: np.ndarray, queries: np.ndarray, k: int):
     return tree.query(queries, k=k)
 
 
-def knn_bruteforce(points: np.ndarray, queries: np.ndarray, k: int, chunk: int = 2048):
-    """Exact brute-force k-NN (small cases only): ties broken by lower index.
+def knn_bruteforce(points: np.ndarray, queries: np.ndarray, k: int, chunk: int = 2048, squared: bool = False):
+    """Exact brute-force k-NN (small cases only): ascending d2, ties broken by lower index.
 
-    Distances use the cKDTree p=2 order ``(dx*dx + dy*dy) + dz*dz`` then sqrt.
+    Distances use the cKDTree p=2 order ``(dx*dx + dy*dy) + dz*dz`` then sqrt; ``squared``
+    returns the d2 themselves (sqrt can merge two distinct d2 into one distance).
     """
     points = np.ascontiguousarray(points, dtype=np.float64)
     queries = np.ascontiguousarray(queries, dtype=np.float64)
@@ -141,9 +142,21 @@ def knn_bruteforce(points: np.ndarray, queries: np.ndarray, k: int, chunk: int =
         dy = q[:, None, 1] - points[None, :, 1]
         dz = q[:, None, 2] - points[None, :, 2]
         d2 = (dx * dx + dy * dy) + dz * dz
-        order = np.argsort(d2, axis=1, kind="stable")[:, :k]
+        if k < d2.shape[1]:
+            # some k smallest per row, put in index order and then sorted stably by d2: the first k of
+            # the full stable sort, except in rows where the k-th d2 ties with one left out (there the
+            # selection's choice is arbitrary); those rows take the full sort
+            part = np.sort(np.argpartition(d2, k - 1, axis=1)[:, :k], axis=1)
+            dp = np.take_along_axis(d2, part, axis=1)
+            order = np.take_along_axis(part, np.argsort(dp, axis=1, kind="stable"), axis=1)
+            cut = (d2 <= dp.max(axis=1, keepdims=True)).sum(axis=1) > k
+            if cut.any():
+                order[cut] = np.argsort(d2[cut], axis=1, kind="stable")[:, :k]
+        else:
+            order = np.argsort(d2, axis=1, kind="stable")[:, :k]
         idx[s : s + chunk] = order
-        dist[s : s + chunk] = np.sqrt(np.take_along_axis(d2, order, axis=1))
+        dk = np.take_along_axis(d2, order, axis=1)
+        dist[s : s + chunk] = dk if squared else np.sqrt(dk)
     return dist, idx
 
 
@@ -185,6 +198,13 @@ def interp_points(points, values, queries, method="idw", k=8, power=2.0, knn="kd
         dist, idx = knn_kdtree(points, queries, k)
     else:
         dist, idx = knn_bruteforce(points, queries, k)
+    return interp_from_lists(dist, idx, values, method, power)
+
+
+def interp_from_lists(dist, idx, values, method="idw", power=2.0):
+    """The epilogue of ``interp_points`` on given neighbour lists: (M, k) ascending distances and
+    their particle indices (k = 1 for 'nearest') -> (M, 3) float64."""
+    values = np.asarray(values, dtype=np.float64)
     if method == "nearest":
         # NearestNDInterpolator.__call__: values[i] for the single nearest particle
         return values[np.asarray(idx).reshape(-1)]
@@ -303,7 +323,7 @@ def solve_extended(lhs, rhs):
 
 
 def rbf_local_points(points, values, queries, k, kernel="thin_plate_spline", epsilon=None, degree=None,
-                     smoothing=0.0, chunk=2048, solver="lapack"):
+                     smoothing=0.0, chunk=2048, solver="lapack", knn="kdtree"):
     """RBFInterpolator(points, values, neighbors=k, kernel, epsilon, degree, smoothing)(queries).
 
     Per query: KDTree k nearest (``_rbfinterp.py:513``), indices sorted ascending
@@ -313,11 +333,10 @@ def rbf_local_points(points, values, queries, k, kernel="thin_plate_spline", eps
     over the neighbourhood -- solved with LAPACK gesv (numpy batched solve, the same
     dgesv scipy calls at :113), evaluated as ``[phi(||eps*x - eps*y_j||), P((x -
     shift)/scale)] @ coeffs`` (:404-418).  scipy solves each *unique* neighbourhood
-    once; solving it once per query gives the same coefficients.
+    once; solving it once per query gives the same coefficients.  ``knn="bruteforce"`` takes the
+    neighbour sets from ``knn_bruteforce`` instead of the tree.
     Returns (Q, S) float64.  Singular systems raise numpy.linalg.LinAlgError.
     """
-    from scipy.spatial import KDTree
-
     y = np.asarray(points, dtype=np.float64)
     d = np.asarray(values, dtype=np.float64).reshape(len(y), -1)
     x = np.asarray(queries, dtype=np.float64).reshape(-1, 3)
@@ -333,7 +352,7 @@ def rbf_local_points(points, values, queries, k, kernel="thin_plate_spline", eps
     phi = RBF_PHI[kernel]
     R = powers.shape[0]
     m = k + R
-    _, idx = KDTree(y).query(x, k)
+    _, idx = knn_kdtree(y, x, k) if knn == "kdtree" else knn_bruteforce(y, x, k)
     idx = np.sort(np.asarray(idx).reshape(len(x), k), axis=1)
     out = np.empty((len(x), d.shape[1]))
     for c0 in range(0, len(x), chunk):
@@ -790,17 +809,21 @@ def boundary_particles(mask, bounds, sampling_step=1, thickness=1):
     return phys(ix, xmin, xmax, nx), phys(iy, ymin, ymax, ny), phys(iz, zmin, zmax, nz)
 
 
-def outlier_filter(points, values, k=25, threshold=3.0, workers=1):
+def outlier_filter(points, values, k=25, threshold=3.0, workers=1, knn="kdtree"):
     """remove_outliers_knn (filtering.py:5-58) -> (keep mask, median k-th radius).
 
     KDTree(points).query(points, k+1) with column 0 dropped, speed median and MAD over the
-    k neighbours, z = |speed - median| / (MAD + 1e-6) <= threshold."""
+    k neighbours, z = |speed - median| / (MAD + 1e-6) <= threshold.  ``knn="bruteforce"`` takes
+    the k + 1 columns from ``knn_bruteforce`` instead of the tree."""
     from scipy.spatial import KDTree
 
     points = np.asarray(points, dtype=np.float64)
     u, v, w = (np.asarray(values, dtype=np.float64)[:, c] for c in range(3))
     speed = np.sqrt(u**2 + v**2 + w**2)
-    dist, idx = KDTree(points).query(points, k=k + 1, workers=workers)
+    if knn == "kdtree":
+        dist, idx = KDTree(points).query(points, k=k + 1, workers=workers)
+    else:
+        dist, idx = knn_bruteforce(points, points, k + 1)
     nb = idx[:, 1:]
     radius = np.median(dist[:, 1:][:, -1])
     ns = speed[nb]

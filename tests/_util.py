@@ -131,6 +131,49 @@ def hetero_ties_points(points, values, q, k, extra=8):
     return tie, hetero
 
 
+def d2_ties_points(points, values, q, k, extra=8):
+    """(Q,) bool pair (tie, hetero) for query points q, on equality of the SQUARED distances
+    ``(dx*dx + dy*dy) + dz*dz`` of a brute-force search (hetero_ties_points compares the tree's
+    sqrt distances, which merge distinct d2 a few ulps apart; a search that orders by d2, as the
+    GPU's and cKDTree's do, has a unique answer there).
+
+    ``tie``: two of the k + 1 nearest particles have the same d2.  ``hetero``: such a query where a
+    run of equal d2 that touches the first k does not carry one (u, v, w), the only place where two
+    correct searches may give different bits.  A run that reaches past the k + 1 + ``extra``
+    columns searched counts as heterogeneous."""
+    from oracle import cpu_ref
+
+    P = np.asarray(points, dtype=np.float64)
+    q = np.asarray(q, dtype=np.float64).reshape(-1, 3)
+    d2, idx = cpu_ref.knn_bruteforce(P, q, min(k + 1 + extra, len(P)), squared=True)
+    return d2_ties_lists(d2, idx, values, k)
+
+
+def d2_ties_lists(d2, idx, values, k):
+    """d2_ties_points on brute-force lists already made: (Q, kk) ascending d2 (ties by lower index)
+    and their particle indices, kk > k + 1 or kk = n."""
+    Vv = np.asarray(values, dtype=np.float64)
+    Vv = Vv.reshape(len(Vv), -1)
+    kk = d2.shape[1]
+    kb = min(k + 1, kk)
+    eq = d2[:, :-1] == d2[:, 1:]  # (Q, kk - 1): column j ties with column j + 1
+    tie = eq[:, :kb - 1].any(axis=1)
+    vdiff = (Vv[idx[:, :-1]] != Vv[idx[:, 1:]]).any(axis=2)
+    # the run of a pair (j, j + 1) touches the first k when j < k; beyond column k a pair matters
+    # only while it continues a run that began there
+    chain = eq[:, :min(k, kk - 1)].copy()
+    bad = (chain & vdiff[:, :chain.shape[1]]).any(axis=1)
+    if kk - 1 > k:
+        run = eq[:, k - 1].copy()
+        for j in range(k, kk - 1):
+            if not run.any():
+                break
+            run &= eq[:, j]
+            bad |= run & vdiff[:, j]
+        bad |= run & (kk < len(Vv))  # still tied at the last column searched
+    return tie, bad & tie
+
+
 def hetero_ties(points, values, ax, ay, az, k):
     """(tie, hetero) as (nz, ny, nx) bool over a separable grid (see hetero_ties_points)."""
     Z, Y, X = np.meshgrid(az, ay, ax, indexing="ij")

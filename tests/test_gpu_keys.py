@@ -8,6 +8,8 @@ not prove go to an exact rerun (ptv_stats.n_repair_tiles).  These tests cover k 
 64 limit (interpolator.py:139 accepts any k), exact ties everywhere (a particle lattice: every
 boundary is a tie, so the repair path runs), coincident particles (d2 = 0 keys are subnormal
 doubles) and the outlier filter's (k+1)-NN (filtering.py:26) through the same lists.
+Near ties, two different d2 of one truncation on particles with different values (the case with a
+unique right answer), are in tests/test_gpu_near_ties.py.
 """
 import numpy as np
 import pytest
