@@ -307,6 +307,34 @@ typedef struct {
     double ms_total, ms_solve;       /* the call on the device; the LSQR solves alone */
 } ptv_clean_stats;
 
+/*
+ * Variational divergence cleaning (physics.clean_divergence_variational, physics.py:440-514).
+ * Solves (I + lambda_reg D^T D) x = (u, v, w)[fluid] with D = [Dx Dy Dz] of
+ * build_divergence_operators (physics.py:356-438) applied matrix-free, by
+ * scipy.sparse.linalg.cg(A, b, rtol, atol=0, maxiter).  The reference passes rtol (its `tol`) =
+ * 1e-8 and maxiter = 2000 (physics.py:485).  Fields and mask as for ptv_clean_params.
+ * PTV_API_VERSION is not raised for these entry points: the presence of ptv_abi_sizes5 in the
+ * library is the capability probe.
+ */
+typedef struct {
+    int64_t nx, ny, nz;
+    double dx, dy, dz;          /* positive */
+    const uint8_t *fluid_mask;
+    double lambda_reg;          /* >= 0 (negative: PTV_E_UNSUPPORTED, the system is not positive definite) */
+    double rtol;                /* stop when ||r|| < rtol * ||b|| at the top of an iteration */
+    int maxiter;                /* >= 0 */
+} ptv_variational_params;
+
+typedef struct {
+    int64_t n_fluid;  /* fluid voxels (A is 3 n_fluid x 3 n_fluid) */
+    int32_t itn;      /* CG iterations completed */
+    int32_t info;     /* scipy's: 0 converged, maxiter when the iterations ran out */
+    double bnorm, rnorm;  /* ||b||; ||r|| as last summed */
+    double mean_abs_div_initial, mean_abs_div_final; /* mean |div| over fluid of the input / the result */
+    double ms_total, ms_solve; /* the call on the device; the CG solve alone */
+    double ms_iter_median;     /* median ms per CG iteration (over polling batches) */
+} ptv_variational_stats;
+
 /* Library / device management. */
 int ptv_version(void);
 /* sizeof(ptv_particles, ptv_grid, ptv_knn_params, ptv_stats, ptv_rbf_params, ptv_div_params):
@@ -318,6 +346,9 @@ int ptv_abi_sizes2(int64_t out3[3]);
 int ptv_abi_sizes3(int64_t out1[1]);
 /* sizeof(ptv_clean_params, ptv_clean_stats): the same self-check */
 int ptv_abi_sizes4(int64_t out2[2]);
+/* sizeof(ptv_variational_params, ptv_variational_stats): the same self-check.  A library that has
+ * this symbol has the variational entry points (PTV_API_VERSION stays 11). */
+int ptv_abi_sizes5(int64_t out2[2]);
 const char *ptv_last_error(void);
 int ptv_device_count(int *out);
 int ptv_init(int device, ptv_ctx **out);
@@ -465,6 +496,37 @@ int ptv_apply_correction(ptv_ctx *ctx, const ptv_clean_params *prm, const double
  * grid (float64 (nz, ny, nx); solid entries of x are ignored, of y written as 0), host buffers.
  */
 int ptv_laplacian_apply(ptv_ctx *ctx, const ptv_clean_params *prm, const double *x_grid, double *y_grid);
+
+/*
+ * Variational divergence cleaning, host buffers: H2D of the fields and mask, the CG solve on the
+ * device, D2H of the cleaned fields Uo, Vo, Wo (float64 (nz, ny, nx); may be U, V, W themselves).
+ * Replaces clean_divergence_variational (physics.py:440-514).  Solid voxels of the outputs are 0;
+ * solid entries of the inputs are never read by the solve.  A mask without fluid, non-positive
+ * spacings, a non-finite lambda_reg or rtol return PTV_E_ARG, lambda_reg < 0 PTV_E_UNSUPPORTED; the
+ * outputs are not written on any error.  Results agree with the host solver normwise, not bit for
+ * bit; two calls on the same input agree bit for bit.
+ */
+int ptv_clean_variational(ptv_ctx *ctx, const ptv_variational_params *prm, const double *U, const double *V,
+                          const double *W, double *Uo, double *Vo, double *Wo, ptv_variational_stats *st);
+
+/* Same on device pointers (fields, mask, outputs), enqueued on `stream` (NULL = the ctx's own);
+ * synchronises (the stop flag is polled, and the statistics are returned). */
+int ptv_clean_variational_dev(ptv_ctx *ctx, const ptv_variational_params *prm, const double *U, const double *V,
+                              const double *W, double *Uo, double *Vo, double *Wo, void *stream,
+                              ptv_variational_stats *st);
+
+/*
+ * (yu, yv, yw) = A (xu, xv, xw) for A = I + lambda_reg D^T D, every array on the grid (float64
+ * (nz, ny, nx); solid entries of x are ignored, of y written as 0), host buffers.  rtol and maxiter
+ * of prm are not read.
+ */
+int ptv_variational_apply(ptv_ctx *ctx, const ptv_variational_params *prm, const double *xu, const double *xv,
+                          const double *xw, double *yu, double *yv, double *yw);
+
+/* d = Dx xu + Dy xv + Dz xw of build_divergence_operators (physics.py:356-438), on the grid, host
+ * buffers.  lambda_reg, rtol and maxiter of prm are not read. */
+int ptv_divergence_operator_apply(ptv_ctx *ctx, const ptv_variational_params *prm, const double *xu,
+                                  const double *xv, const double *xw, double *d_grid);
 
 /*
  * Last-launch k-NN kernel duration in ms (hipEvent pair recorded around the

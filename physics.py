@@ -14,6 +14,11 @@ Opt-in: with ``PTV_GPU_CLEAN=1`` in the environment, ``clean_divergence_projecti
 reference module, so that the reference's ``clean_divergence`` dispatcher (and ``main.py -d``)
 reaches the GPU solver.  It is not the default because that solver agrees with the host's ``lsqr``
 normwise, not bit for bit (INTEGRATION.md).
+
+A second, independent opt-in: with ``PTV_GPU_CLEAN_VARIATIONAL=1``, ``clean_divergence_variational``
+(physics.py:440-514) is replaced the same way, so that the reference's dispatcher (and ``main.py -d
+--cleaning-method variational``) reaches the GPU CG solve.  ``PTV_GPU_CLEAN=1`` alone leaves the
+variational method on the host.
 """
 import importlib.util as _ilu
 import os as _os
@@ -24,6 +29,7 @@ from ptv_interpolation_amd.physics import compute_consistent_divergence as _gpu_
 
 compute_consistent_divergence = _gpu_divergence
 _GPU_CLEAN = _os.environ.get("PTV_GPU_CLEAN", "") == "1"
+_GPU_CLEAN_VARIATIONAL = _os.environ.get("PTV_GPU_CLEAN_VARIATIONAL", "") == "1"
 
 _ROOT = _os.path.dirname(_os.path.abspath(__file__))
 
@@ -62,3 +68,7 @@ if _GPU_CLEAN:
         _ref.apply_consistent_correction = _gpu.apply_consistent_correction
     else:
         clean_divergence = _gpu.clean_divergence
+if _GPU_CLEAN_VARIATIONAL:
+    clean_divergence_variational = _gpu.clean_divergence_variational
+    if _ref is not None:
+        _ref.clean_divergence_variational = _gpu.clean_divergence_variational

@@ -126,6 +126,21 @@ class CleanStats(C.Structure):
         return d
 
 
+class VariationalParams(C.Structure):
+    _fields_ = [("nx", C.c_int64), ("ny", C.c_int64), ("nz", C.c_int64), ("dx", C.c_double), ("dy", C.c_double),
+                ("dz", C.c_double), ("fluid_mask", _u8p), ("lambda_reg", C.c_double), ("rtol", C.c_double),
+                ("maxiter", C.c_int)]
+
+
+class VariationalStats(C.Structure):
+    _fields_ = [("n_fluid", C.c_int64), ("itn", C.c_int32), ("info", C.c_int32), ("bnorm", C.c_double),
+                ("rnorm", C.c_double), ("mean_abs_div_initial", C.c_double), ("mean_abs_div_final", C.c_double),
+                ("ms_total", C.c_double), ("ms_solve", C.c_double), ("ms_iter_median", C.c_double)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 MASK_BOOL = 0
 MASK_BITS = 1
 
@@ -204,6 +219,13 @@ EXPORTS = {
                                            C.c_void_p, C.POINTER(CleanStats)]),
     "ptv_apply_correction": (C.c_int, [C.c_void_p, C.POINTER(CleanParams), _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "ptv_laplacian_apply": (C.c_int, [C.c_void_p, C.POINTER(CleanParams), _dp, _dp]),
+    "ptv_abi_sizes5": (C.c_int, [C.POINTER(C.c_int64)]),
+    "ptv_clean_variational": (C.c_int, [C.c_void_p, C.POINTER(VariationalParams), _dp, _dp, _dp, _dp, _dp, _dp,
+                                        C.POINTER(VariationalStats)]),
+    "ptv_clean_variational_dev": (C.c_int, [C.c_void_p, C.POINTER(VariationalParams), _dp, _dp, _dp, _dp, _dp, _dp,
+                                            C.c_void_p, C.POINTER(VariationalStats)]),
+    "ptv_variational_apply": (C.c_int, [C.c_void_p, C.POINTER(VariationalParams), _dp, _dp, _dp, _dp, _dp, _dp]),
+    "ptv_divergence_operator_apply": (C.c_int, [C.c_void_p, C.POINTER(VariationalParams), _dp, _dp, _dp, _dp]),
     "ptv_last_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     "ptv_debug_stamps": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double)]),
 }
@@ -299,6 +321,13 @@ def abi_sizes4():
     out = (C.c_int64 * 2)()
     check(lib().ptv_abi_sizes4(out))
     return list(out), [C.sizeof(CleanParams), C.sizeof(CleanStats)]
+
+
+def abi_sizes5():
+    """(C sizeof, ctypes sizeof) of ptv_variational_params and ptv_variational_stats."""
+    out = (C.c_int64 * 2)()
+    check(lib().ptv_abi_sizes5(out))
+    return list(out), [C.sizeof(VariationalParams), C.sizeof(VariationalStats)]
 
 
 class Triangulation:
@@ -830,3 +859,50 @@ class Context:
         y = np.empty_like(x)
         check(lib().ptv_laplacian_apply(self.h, C.byref(prm), as_dp(x), as_dp(y)))
         return y
+
+    # -- divergence cleaning, variational method (physics.py:356-514) ------
+    @staticmethod
+    def _variational_params(shape, fluid_mask, dx, dy, dz, lambda_reg=0.0, rtol=0.0, maxiter=0):
+        nz, ny, nx = shape
+        mk = np.ascontiguousarray(fluid_mask, dtype=bool).view(np.uint8).reshape(nz, ny, nx)
+        prm = VariationalParams(nx, ny, nz, float(dx), float(dy), float(dz), mk.ctypes.data_as(_u8p),
+                                float(lambda_reg), float(rtol), int(maxiter))
+        return prm, mk  # mk keeps the mask bytes alive for the call
+
+    def clean_variational(self, u, v, w, fluid_mask, dx, dy, dz, lambda_reg=1e3, rtol=1e-8, maxiter=2000):
+        """Variational cleaning of float64 (nz, ny, nx) host fields (physics.py:440-514 with its cg
+        arguments as defaults); returns ``((u_c, v_c, w_c), stats dict)``."""
+        f = [np.ascontiguousarray(a, dtype=np.float64) for a in (u, v, w)]
+        prm, _mk = self._variational_params(f[0].shape, fluid_mask, dx, dy, dz, lambda_reg, rtol, maxiter)
+        out = [np.empty_like(a) for a in f]
+        st = VariationalStats()
+        check(lib().ptv_clean_variational(self.h, C.byref(prm), *[as_dp(a) for a in f], *[as_dp(a) for a in out],
+                                          C.byref(st)))
+        return tuple(out), st.as_dict()
+
+    def clean_variational_dev(self, nx, ny, nz, ptrs, mask_ptr, out_ptrs, dx, dy, dz, lambda_reg=1e3, rtol=1e-8,
+                              maxiter=2000, stream=0):
+        """Device-pointer variational cleaning (float64 fields, uint8 mask and outputs resident in HBM;
+        the outputs may be the inputs); returns the stats dict."""
+        prm = VariationalParams(nx, ny, nz, float(dx), float(dy), float(dz), C.cast(C.c_void_p(mask_ptr), _u8p),
+                                float(lambda_reg), float(rtol), int(maxiter))
+        st = VariationalStats()
+        check(lib().ptv_clean_variational_dev(self.h, C.byref(prm), *[dev_dp(p) for p in ptrs],
+                                              *[dev_dp(p) for p in out_ptrs], C.c_void_p(stream or 0), C.byref(st)))
+        return st.as_dict()
+
+    def variational_apply(self, xu, xv, xw, fluid_mask, dx, dy, dz, lambda_reg):
+        """``A @ x`` for A = I + lambda D^T D of physics.py:460-480, x and the result on the grid."""
+        f = [np.ascontiguousarray(a, dtype=np.float64) for a in (xu, xv, xw)]
+        prm, _mk = self._variational_params(f[0].shape, fluid_mask, dx, dy, dz, lambda_reg)
+        out = [np.empty_like(a) for a in f]
+        check(lib().ptv_variational_apply(self.h, C.byref(prm), *[as_dp(a) for a in f], *[as_dp(a) for a in out]))
+        return tuple(out)
+
+    def divergence_operator_apply(self, xu, xv, xw, fluid_mask, dx, dy, dz):
+        """``Dx @ xu + Dy @ xv + Dz @ xw`` for the operators of physics.py:356-438, on the grid."""
+        f = [np.ascontiguousarray(a, dtype=np.float64) for a in (xu, xv, xw)]
+        prm, _mk = self._variational_params(f[0].shape, fluid_mask, dx, dy, dz)
+        d = np.empty_like(f[0])
+        check(lib().ptv_divergence_operator_apply(self.h, C.byref(prm), *[as_dp(a) for a in f], as_dp(d)))
+        return d

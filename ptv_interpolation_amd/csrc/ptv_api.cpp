@@ -76,6 +76,16 @@ int ptv_abi_sizes4(int64_t out2[2]) {
     return PTV_OK;
 }
 
+int ptv_abi_sizes5(int64_t out2[2]) {
+    if (!out2) {
+        set_error("ptv_abi_sizes5: out is NULL");
+        return PTV_E_ARG;
+    }
+    out2[0] = (int64_t)sizeof(ptv_variational_params);
+    out2[1] = (int64_t)sizeof(ptv_variational_stats);
+    return PTV_OK;
+}
+
 const char *ptv_last_error(void) { return g_last_error.c_str(); }
 
 int ptv_device_count(int *out) {
@@ -793,6 +803,123 @@ int ptv_laplacian_apply(ptv_ctx *c, const ptv_clean_params *prm, const double *x
     PTV_TRY(c->clean_fld[1].ensure(n));
     PTV_TRY(launch_clean_laplacian(g, c->mask.p, c->clean_fld[0].p, c->clean_fld[1].p, s));
     PTV_HIP(hipMemcpyAsync(y_grid, c->clean_fld[1].p, n * sizeof(double), hipMemcpyDeviceToHost, s));
+    PTV_HIP(hipStreamSynchronize(s));
+    return PTV_OK;
+}
+
+// ---- variational divergence cleaning (ptv_variational.hip) ----
+static int var_check(ptv_ctx *c, const ptv_variational_params *prm, VarGrid &g) {
+    if (!c || !prm) {
+        set_error("NULL context/params");
+        return PTV_E_ARG;
+    }
+    if (!prm->fluid_mask) {
+        set_error("variational: the fluid mask is required");
+        return PTV_E_ARG;
+    }
+    if (prm->nx <= 0 || prm->ny <= 0 || prm->nz <= 0 || prm->nx > (1 << 30) || prm->ny > (1 << 30) ||
+        prm->nz > (1 << 30) || prm->nx * prm->ny * prm->nz > 0x7fff0000LL) {
+        set_error("variational: dimensions must be positive, with fewer than 2^31 voxels");
+        return PTV_E_ARG;
+    }
+    g.nx = (int)prm->nx;
+    g.ny = (int)prm->ny;
+    g.nz = (int)prm->nz;
+    g.dx = prm->dx;
+    g.dy = prm->dy;
+    g.dz = prm->dz;
+    return PTV_OK;
+}
+
+// host grids -> c->var_fld[0..nf), mask -> c->mask; var_fld[nf..nbuf) are sized for the results
+static int var_upload(ptv_ctx *c, const ptv_variational_params *prm, const double *const *src, int nf, int nbuf,
+                      hipStream_t s) {
+    const size_t n = (size_t)(prm->nx * prm->ny * prm->nz);
+    for (int i = 0; i < nbuf; ++i) PTV_TRY(c->var_fld[i].ensure(n));
+    for (int i = 0; i < nf; ++i)
+        PTV_HIP(hipMemcpyAsync(c->var_fld[i].p, src[i], n * sizeof(double), hipMemcpyHostToDevice, s));
+    PTV_TRY(c->mask.ensure(n));
+    PTV_HIP(hipMemcpyAsync(c->mask.p, prm->fluid_mask, n, hipMemcpyHostToDevice, s));
+    return PTV_OK;
+}
+
+int ptv_clean_variational_dev(ptv_ctx *c, const ptv_variational_params *prm, const double *U, const double *V,
+                              const double *W, double *Uo, double *Vo, double *Wo, void *stream,
+                              ptv_variational_stats *st) {
+    VarGrid g{};
+    PTV_TRY(var_check(c, prm, g));
+    if (!U || !V || !W || !Uo || !Vo || !Wo) {
+        set_error("variational: NULL field or output");
+        return PTV_E_ARG;
+    }
+    PTV_HIP(hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    const VarSolve sv{prm->lambda_reg, prm->rtol, prm->maxiter};
+    return variational_run(c->var, g, sv, prm->fluid_mask, U, V, W, Uo, Vo, Wo, s, st);
+}
+
+int ptv_clean_variational(ptv_ctx *c, const ptv_variational_params *prm, const double *U, const double *V,
+                          const double *W, double *Uo, double *Vo, double *Wo, ptv_variational_stats *st) {
+    VarGrid g{};
+    PTV_TRY(var_check(c, prm, g));
+    if (!U || !V || !W || !Uo || !Vo || !Wo) {
+        set_error("variational: NULL field or output");
+        return PTV_E_ARG;
+    }
+    PTV_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const double *src[3] = {U, V, W};
+    PTV_TRY(var_upload(c, prm, src, 3, 3, s));
+    const VarSolve sv{prm->lambda_reg, prm->rtol, prm->maxiter};
+    double *d[3] = {c->var_fld[0].p, c->var_fld[1].p, c->var_fld[2].p};
+    PTV_TRY(variational_run(c->var, g, sv, c->mask.p, d[0], d[1], d[2], d[0], d[1], d[2], s, st));
+    const size_t nbytes = (size_t)(prm->nx * prm->ny * prm->nz) * sizeof(double);
+    double *dst[3] = {Uo, Vo, Wo};
+    for (int i = 0; i < 3; ++i) PTV_HIP(hipMemcpyAsync(dst[i], d[i], nbytes, hipMemcpyDeviceToHost, s));
+    PTV_HIP(hipStreamSynchronize(s));
+    return PTV_OK;
+}
+
+int ptv_divergence_operator_apply(ptv_ctx *c, const ptv_variational_params *prm, const double *xu, const double *xv,
+                                  const double *xw, double *d_grid) {
+    VarGrid g{};
+    PTV_TRY(var_check(c, prm, g));
+    if (!xu || !xv || !xw || !d_grid) {
+        set_error("divergence_operator_apply: NULL input or output");
+        return PTV_E_ARG;
+    }
+    PTV_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const double *src[3] = {xu, xv, xw};
+    PTV_TRY(var_upload(c, prm, src, 3, 4, s));
+    PTV_TRY(launch_var_divergence(g, c->mask.p, c->var_fld[0].p, c->var_fld[1].p, c->var_fld[2].p, c->var_fld[3].p, s));
+    const size_t n = (size_t)(prm->nx * prm->ny * prm->nz);
+    PTV_HIP(hipMemcpyAsync(d_grid, c->var_fld[3].p, n * sizeof(double), hipMemcpyDeviceToHost, s));
+    PTV_HIP(hipStreamSynchronize(s));
+    return PTV_OK;
+}
+
+int ptv_variational_apply(ptv_ctx *c, const ptv_variational_params *prm, const double *xu, const double *xv,
+                          const double *xw, double *yu, double *yv, double *yw) {
+    VarGrid g{};
+    PTV_TRY(var_check(c, prm, g));
+    if (!xu || !xv || !xw || !yu || !yv || !yw) {
+        set_error("variational_apply: NULL input or output");
+        return PTV_E_ARG;
+    }
+    PTV_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const double *src[3] = {xu, xv, xw};
+    PTV_TRY(var_upload(c, prm, src, 3, 6, s));
+    const size_t n = (size_t)(prm->nx * prm->ny * prm->nz);
+    PTV_TRY(c->var.d.ensure(n));
+    double *f[6];
+    for (int i = 0; i < 6; ++i) f[i] = c->var_fld[i].p;
+    PTV_TRY(launch_var_divergence(g, c->mask.p, f[0], f[1], f[2], c->var.d.p, s));
+    PTV_TRY(launch_var_adjoint(g, prm->lambda_reg, c->mask.p, c->var.d.p, f[0], f[1], f[2], f[3], f[4], f[5],
+                               c->var.part, s));
+    double *dst[3] = {yu, yv, yw};
+    for (int i = 0; i < 3; ++i) PTV_HIP(hipMemcpyAsync(dst[i], f[3 + i], n * sizeof(double), hipMemcpyDeviceToHost, s));
     PTV_HIP(hipStreamSynchronize(s));
     return PTV_OK;
 }

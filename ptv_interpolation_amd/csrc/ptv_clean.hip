@@ -32,17 +32,17 @@
 #include <algorithm>
 
 #include "ptv_clean.hpp"
+#include "ptv_grid_vec.hpp"
 #include "ptv_kernels.hpp"
-#include "ptv_wave.hpp"
 
 namespace ptv {
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kItems = 4;   // element groups per thread (independent loads in flight)
+constexpr int kThreads = kGridThreads;
+constexpr int kItems = kGridItems;
 constexpr int kPoll = 8;    // LSQR iterations between two polls of the stop flag
-constexpr int kFinalThreads = 256;
+constexpr int kFinalThreads = kGridFinalThreads;
 
 // device-resident LSQR state (doubles; names follow scipy's lsqr)
 enum {
@@ -58,10 +58,7 @@ constexpr int kRepLen = 3 + PTV_CLEAN_MAX_OUTER + 1;
 
 enum Phase { PH_DIVSTATS = 0, PH_INIT_BETA, PH_INIT_ALFA, PH_BETA, PH_ALFA, PH_TEST, PH_NAN };
 
-struct CleanArgs {
-    int nx, ny, nz;
-    unsigned n;          // voxels (< 2^31)
-    unsigned plane;      // nx * ny
+struct CleanArgs : GridDims {
     double hx, hy, hz;   // 1.0 / (h ** 2) per axis (physics.py:68)
     double dx, dy, dz;
 };
@@ -70,75 +67,6 @@ struct LsqrCfg {
     double damp, atol, btol, ctol;
     int iter_lim;
 };
-
-template <int VEC>
-struct DV {
-    double e[VEC];
-};
-template <int VEC>
-__device__ __forceinline__ DV<VEC> ldd(const double *p) {
-    DV<VEC> r;
-    if constexpr (VEC == 2) {
-        const double2 q = *reinterpret_cast<const double2 *>(p);
-        r.e[0] = q.x;
-        r.e[1] = q.y;
-    } else {
-        r.e[0] = p[0];
-    }
-    return r;
-}
-template <int VEC>
-__device__ __forceinline__ void std_(double *p, const DV<VEC> &v) {
-    if constexpr (VEC == 2) *reinterpret_cast<double2 *>(p) = make_double2(v.e[0], v.e[1]);
-    else p[0] = v.e[0];
-}
-template <int VEC>
-struct MV {
-    uint8_t e[VEC];
-};
-template <int VEC>
-__device__ __forceinline__ MV<VEC> ldmk(const uint8_t *p) {
-    MV<VEC> r;
-    if constexpr (VEC == 2) {
-        const uint16_t q = *reinterpret_cast<const uint16_t *>(p);
-        r.e[0] = (uint8_t)(q & 0xff);
-        r.e[1] = (uint8_t)(q >> 8);
-    } else {
-        r.e[0] = p[0];
-    }
-    return r;
-}
-
-// position of a thread's element group; a group of VEC lies inside one x row (nx % VEC == 0)
-struct Pos {
-    unsigned i;
-    int x, y, z;
-};
-template <int VEC>
-__device__ __forceinline__ bool group_pos(const CleanArgs &a, int item, Pos &p) {
-    const unsigned long long i =
-        ((unsigned long long)blockIdx.x * kItems + item) * (kThreads * VEC) + threadIdx.x * VEC;
-    if (i >= a.n) return false;
-    p.i = (unsigned)i;
-    p.z = (int)(p.i / a.plane);
-    const unsigned r = p.i - (unsigned)p.z * a.plane;
-    p.y = (int)(r / (unsigned)a.nx);
-    p.x = (int)(r - (unsigned)p.y * (unsigned)a.nx);
-    return true;
-}
-
-// block sum in a fixed order: wave64 DPP tree, then the 4 wave sums in wave order
-__device__ __forceinline__ double block_sum(double v) {
-    __shared__ double lds[kThreads / 64];
-    __syncthreads();  // a previous call's reads of lds
-    v = group_reduce<0x3f>(v, OpAdd{});
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double s = lds[0];
-#pragma unroll
-    for (int k = 1; k < kThreads / 64; ++k) s += lds[k];
-    return s;
-}
 
 // (A (sc * X))_i for the VEC elements of a group, o.e[e] = 0 where the voxel is solid.  Neighbour
 // offsets are clamped at the domain faces, so every load is in bounds and unconditional; a face or
@@ -260,36 +188,6 @@ __global__ __launch_bounds__(kThreads) void k_update(CleanArgs a, const double *
     }
     ss = block_sum(ss);
     if (threadIdx.x == 0) part[blockIdx.x] = ss;
-}
-
-// partial sums over fluid voxels of div, |div| and 1 (rows 0, 1, 2 of part)
-template <int VEC>
-__global__ __launch_bounds__(kThreads) void k_div_stats(CleanArgs a, const double *__restrict__ D,
-                                                        const uint8_t *__restrict__ M, double *__restrict__ part,
-                                                        unsigned npart) {
-    double s = 0.0, sa = 0.0, cnt = 0.0;
-#pragma unroll
-    for (int it = 0; it < kItems; ++it) {
-        Pos p;
-        if (!group_pos<VEC>(a, it, p)) break;
-        const MV<VEC> mc = ldmk<VEC>(M + p.i);
-        const DV<VEC> d = ldd<VEC>(D + p.i);
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) {
-            if (!mc.e[e]) continue;
-            s += d.e[e];
-            sa += fabs(d.e[e]);
-            cnt += 1.0;
-        }
-    }
-    s = block_sum(s);
-    sa = block_sum(sa);
-    cnt = block_sum(cnt);
-    if (threadIdx.x == 0) {
-        part[blockIdx.x] = s;
-        part[npart + blockIdx.x] = sa;
-        part[2 * npart + blockIdx.x] = cnt;
-    }
 }
 
 // LSQR's first u: b = div[fluid] - mean(div[fluid]) (physics.py:182-183), partial sums of b^2
@@ -605,14 +503,6 @@ int make_args(const CleanGrid &g, CleanArgs &a) {
     return PTV_OK;
 }
 
-inline bool aligned(const void *p, size_t n) { return ((uintptr_t)p % n) == 0; }
-
-// blocks of a pass over n voxels with VEC elements per lane
-inline unsigned blocks_for(unsigned n, int vec) {
-    const unsigned per = (unsigned)(kThreads * kItems * vec);
-    return (n + per - 1) / per;
-}
-
 // one LSQR solve on the vectors of `wk`; u holds b on entry, x the solution on exit
 struct Solver {
     CleanWork &wk;
@@ -705,30 +595,10 @@ struct Solver {
         float ms = 0.f;
         PTV_HIP(hipEventElapsedTime(&ms, wk.ev[2], wk.ev[4 + batches]));
         ms_solve = ms;
-        // per-iteration time: batches all of whose iterations ran before the stop
-        const int itn = (int)h_final[S_ITN];
-        std::vector<double> per;
-        int seen = 0;
-        for (int b = 0; b < batches; ++b) {
-            seen += batch_iters[b];
-            if (seen > itn) break;
-            PTV_HIP(hipEventElapsedTime(&ms, wk.ev[3 + b], wk.ev[4 + b]));
-            per.push_back((double)ms / batch_iters[b]);
-        }
-        if (per.empty()) {
-            ms_iter_median = itn > 0 ? ms_solve / itn : 0.0;
-        } else {
-            std::sort(per.begin(), per.end());
-            ms_iter_median = per[per.size() / 2];
-        }
+        PTV_TRY(median_iter_ms(wk.ev, 3, batch_iters, (int)h_final[S_ITN], ms_solve, ms_iter_median));
         return PTV_OK;
     }
 };
-
-template <typename... P>
-bool all_aligned16(P... p) {
-    return (aligned(p, 16) && ...);
-}
 
 }  // namespace
 

@@ -14,6 +14,7 @@
 #include "ptv_kernels.hpp"
 #include "ptv_knn_big.hpp"
 #include "ptv_own.hpp"
+#include "ptv_variational.hpp"
 
 namespace ptv {
 
@@ -94,6 +95,8 @@ struct ptv_ctx {
     ptv::DevBuf<long long> lin_flags;                                 // linear: voxels left to the brute force
     ptv::CleanWork clean;                                             // divergence cleaning: LSQR vectors, state
     ptv::DevBuf<double> clean_fld[4];                                 // its host calls: U, V, W (in place), phi / x
+    ptv::VarWork var;                                                 // variational cleaning: CG vectors, state
+    ptv::DevBuf<double> var_fld[6];                                   // its host calls: fields (in place) / x, y
     ptv::PinnedBuf<double> h_bbox;                                    // pinned, kHostWords doubles
     ptv::PinnedBuf<unsigned long long> h_misc;  // pinned scratch words (cull count, halo bound, repair count)
     ptv_stats last{};

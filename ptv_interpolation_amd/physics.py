@@ -15,7 +15,14 @@ device for the whole call.  ``apply_consistent_correction`` (physics.py:110-147)
 to the reference; the solve agrees with the host solver normwise, not bit for bit (its norms are
 summed in another order, and thousands of Lanczos steps amplify the last bit).
 
-``solve_poisson`` and the variational method (physics.py:264-345, :440-514) stay with the reference.
+``clean_divergence_variational`` (physics.py:440-514) runs on the GPU as well: scipy's ``cg`` on
+I + lambda D^T D restated matrix-free (csrc/ptv_variational.hip behind ``ptv_clean_variational``;
+DESIGN.md §17).  It does not depend on the ``tol=`` keyword that scipy 1.14 removed from ``cg``,
+which the reference's call still uses.  The package's own ``clean_divergence`` dispatcher keeps
+refusing ``method='variational'``; call ``clean_divergence_variational`` directly, or opt in through
+the repo-root shim (``PTV_GPU_CLEAN_VARIATIONAL=1``).
+
+``solve_poisson`` (physics.py:264-345) stays with the reference.
 """
 from __future__ import annotations
 
@@ -24,7 +31,7 @@ import numpy as np
 from . import _lib, launcher
 
 __all__ = ["compute_consistent_divergence", "apply_consistent_correction", "clean_divergence_projection",
-           "clean_divergence"]
+           "clean_divergence_variational", "clean_divergence"]
 
 
 def _result_dtype(ft, h):
@@ -128,6 +135,35 @@ def clean_divergence_projection(u, v, w, mask, dx, dy, dz, iterations=3):
     print(f"  [Final] Net X-Flux (mid-plane): {st['flux_final']:.4e}")
     print("="*40 + "\n")
     clean_divergence_projection.last_stats = st
+    return u_c, v_c, w_c
+
+
+def clean_divergence_variational(u, v, w, mask, dx, dy, dz, iterations=1, lambda_reg=1e3):
+    """physics.py:440-514 on the GPU: minimises ||U - U0||^2 + lambda ||div U||^2 by CG with the
+    reference's ``tol=1e-8, maxiter=2000``; prints the reference's report and returns
+    ``(u_c, v_c, w_c)``.  ``iterations`` is unused, as in the reference."""
+    mask = _clean_args(u, v, w, mask)
+    lam = float(lambda_reg)
+    if not np.isfinite(lam):
+        raise ValueError(f"lambda_reg must be finite, got {lambda_reg!r}")
+    if lam < 0:
+        raise NotImplementedError(f"lambda_reg = {lambda_reg!r} < 0: the system is not positive definite")
+    (u_c, v_c, w_c), st = _ctx().clean_variational(u, v, w, mask, float(dx), float(dy), float(dz), lambda_reg=lam,
+                                                   rtol=1e-8, maxiter=2000)
+    n = 3 * st["n_fluid"]
+    print(f"Starting Variational Divergence Cleaning (lambda={lambda_reg})...")
+    print(f"  Solving Variational System (A: {n}x{n})...")
+    if st["info"] > 0:
+        print(f"  Warning: CG did not converge after {st['info']} iterations.")
+    m_div_init, m_div_final = st["mean_abs_div_initial"], st["mean_abs_div_final"]
+    print("\n" + "="*40)
+    print("VARIATIONAL CLEANING COMPLETE")
+    print(f"Mean Abs Div (Initial): {m_div_init:.6e}")
+    print(f"Mean Abs Div (Final):   {m_div_final:.6e}")
+    reduction = m_div_init / m_div_final if m_div_final > 0 else float('inf')
+    print(f"Total Reduction:        {reduction:.2f}x")
+    print("="*40 + "\n")
+    clean_divergence_variational.last_stats = st
     return u_c, v_c, w_c
 
 
