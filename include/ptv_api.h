@@ -335,6 +335,45 @@ typedef struct {
     double ms_iter_median;     /* median ms per CG iteration (over polling batches) */
 } ptv_variational_stats;
 
+/*
+ * Flow analysis (velocity_analysis.py: compute_strain_rate :10-63, compute_viscous_dissipation
+ * :65-92, compute_vorticity :94-120, compute_astarita_flow_type :151-188; the sums feed
+ * compute_permeability :122-149 and the report of analyze_flow.py:335-368).  Fields, outputs and
+ * the uint8 fluid mask (nonzero = fluid; NULL = nothing is zeroed) are (nz, ny, nx) C order; the
+ * slab and halo fields mean exactly what they mean in ptv_div_params.  Outputs have the fields'
+ * dtype.  spacing_strong selects numpy's division rule for float32 fields: 0 = Python-float
+ * spacings (float32 division by (float)h), 1 = np.float64 spacings (float64 division, the quotient
+ * rounded to float32); float64 fields ignore it.  Results are bit-identical to the reference.
+ * PTV_API_VERSION is not raised: the presence of ptv_abi_sizes6 is the capability probe.
+ */
+#define PTV_FLOW_STRAIN 0
+#define PTV_FLOW_DISSIPATION 1
+#define PTV_FLOW_VORTICITY 2
+#define PTV_FLOW_TYPE 3
+typedef struct {
+    int64_t nx, ny, nz;
+    int64_t z_begin, z_end;
+    int edge_lo, edge_hi;
+    int field_dtype;      /* PTV_F64 | PTV_F32 */
+    int spacing_strong;   /* float32 fields: 0 weak (Python float), 1 strong (np.float64) */
+    double dx, dy, dz;    /* positive and finite */
+    double viscosity;     /* dissipation = (T)viscosity * S * S */
+    const uint8_t *fluid_mask; /* may be NULL */
+} ptv_flow_params;
+
+/* Sums are float64 whatever the field dtype and the same bits on every call (fixed order, no
+ * atomics).  Indices of the arrays: PTV_FLOW_*; entries of outputs not requested are 0.  max / min
+ * propagate NaN as np.max / np.min do.  Outputs are 0 at solid voxels, so sum_fluid[k] (the sum of
+ * out[mask]) equals sum[k] bit for bit; both are given because the report divides them by
+ * different counts. */
+typedef struct {
+    int64_t n_voxels, n_fluid;       /* voxels of the computed planes; fluid ones (= n_voxels without a mask) */
+    double sum_u, sum_v, sum_w;      /* over the computed planes; the elementwise mode: the sums of its strain
+                                      * and vorticity_mag inputs in sum_u and sum_v (0 when not given) */
+    double sum[4], sum_fluid[4], max[4], min[4];
+    double ms_stencil;               /* the kernels of the call, hipEvent based */
+} ptv_flow_stats;
+
 /* Library / device management. */
 int ptv_version(void);
 /* sizeof(ptv_particles, ptv_grid, ptv_knn_params, ptv_stats, ptv_rbf_params, ptv_div_params):
@@ -349,6 +388,9 @@ int ptv_abi_sizes4(int64_t out2[2]);
 /* sizeof(ptv_variational_params, ptv_variational_stats): the same self-check.  A library that has
  * this symbol has the variational entry points (PTV_API_VERSION stays 11). */
 int ptv_abi_sizes5(int64_t out2[2]);
+/* sizeof(ptv_flow_params, ptv_flow_stats): the same self-check.  A library that has this symbol has
+ * the flow analysis entry points (PTV_API_VERSION stays 11). */
+int ptv_abi_sizes6(int64_t out2[2]);
 const char *ptv_last_error(void);
 int ptv_device_count(int *out);
 int ptv_init(int device, ptv_ctx **out);
@@ -527,6 +569,34 @@ int ptv_variational_apply(ptv_ctx *ctx, const ptv_variational_params *prm, const
  * buffers.  lambda_reg, rtol and maxiter of prm are not read. */
 int ptv_divergence_operator_apply(ptv_ctx *ctx, const ptv_variational_params *prm, const double *xu,
                                   const double *xv, const double *xw, double *d_grid);
+
+/*
+ * Flow analysis, host buffers: H2D of the fields and mask, one stencil pass, D2H of the requested
+ * outputs.  strain, dissipation, vorticity, flow_type: (z_end - z_begin, ny, nx) of the fields'
+ * dtype, each may be NULL (not computed, not stored).  nx, ny or nz below 2 returns PTV_E_ARG
+ * (np.gradient raises ValueError); an empty plane range returns PTV_OK and zero statistics.
+ */
+int ptv_flow_analysis(ptv_ctx *ctx, const ptv_flow_params *prm, const void *U, const void *V, const void *W,
+                      void *strain, void *dissipation, void *vorticity, void *flow_type, ptv_flow_stats *st);
+
+/* Same on device pointers (fields, mask, outputs), enqueued on `stream` (NULL = the ctx's own);
+ * synchronises (the statistics are returned). */
+int ptv_flow_analysis_dev(ptv_ctx *ctx, const ptv_flow_params *prm, const void *U, const void *V, const void *W,
+                          void *strain, void *dissipation, void *vorticity, void *flow_type, void *stream,
+                          ptv_flow_stats *st);
+
+/*
+ * Elementwise mode for a caller that holds S (and O) rather than u, v, w: dissipation =
+ * (T)viscosity * S * S (compute_viscous_dissipation) and / or flow_type = (S - O) / (S + O) where
+ * S + O > (T)1e-15, else 0 (compute_astarita_flow_type), 0 at solid voxels, over all nz * ny * nx
+ * voxels; the slab, halo and spacing fields of prm are not read.  vorticity_mag is needed for
+ * flow_type only.  The statistics of the outputs and the counts are filled as above.
+ */
+int ptv_flow_derived(ptv_ctx *ctx, const ptv_flow_params *prm, const void *strain, const void *vorticity_mag,
+                     void *dissipation, void *flow_type, ptv_flow_stats *st);
+
+int ptv_flow_derived_dev(ptv_ctx *ctx, const ptv_flow_params *prm, const void *strain, const void *vorticity_mag,
+                         void *dissipation, void *flow_type, void *stream, ptv_flow_stats *st);
 
 /*
  * Last-launch k-NN kernel duration in ms (hipEvent pair recorded around the

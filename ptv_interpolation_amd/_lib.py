@@ -141,6 +141,28 @@ class VariationalStats(C.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+FLOW_OUTPUTS = ("strain_rate", "dissipation", "vorticity", "flow_type")  # PTV_FLOW_* order
+
+
+class FlowParams(C.Structure):
+    _fields_ = [("nx", C.c_int64), ("ny", C.c_int64), ("nz", C.c_int64), ("z_begin", C.c_int64),
+                ("z_end", C.c_int64), ("edge_lo", C.c_int), ("edge_hi", C.c_int), ("field_dtype", C.c_int),
+                ("spacing_strong", C.c_int), ("dx", C.c_double), ("dy", C.c_double), ("dz", C.c_double),
+                ("viscosity", C.c_double), ("fluid_mask", _u8p)]
+
+
+class FlowStats(C.Structure):
+    _fields_ = [("n_voxels", C.c_int64), ("n_fluid", C.c_int64), ("sum_u", C.c_double), ("sum_v", C.c_double),
+                ("sum_w", C.c_double), ("sum", C.c_double * 4), ("sum_fluid", C.c_double * 4),
+                ("max", C.c_double * 4), ("min", C.c_double * 4), ("ms_stencil", C.c_double)]
+
+    def as_dict(self):
+        d = {f: getattr(self, f) for f, t in self._fields_ if not hasattr(t, "_length_")}
+        for f in ("sum", "sum_fluid", "max", "min"):
+            d[f] = dict(zip(FLOW_OUTPUTS, getattr(self, f)))
+        return d
+
+
 MASK_BOOL = 0
 MASK_BITS = 1
 
@@ -226,6 +248,13 @@ EXPORTS = {
                                             C.c_void_p, C.POINTER(VariationalStats)]),
     "ptv_variational_apply": (C.c_int, [C.c_void_p, C.POINTER(VariationalParams), _dp, _dp, _dp, _dp, _dp, _dp]),
     "ptv_divergence_operator_apply": (C.c_int, [C.c_void_p, C.POINTER(VariationalParams), _dp, _dp, _dp, _dp]),
+    "ptv_abi_sizes6": (C.c_int, [C.POINTER(C.c_int64)]),
+    "ptv_flow_analysis": (C.c_int, [C.c_void_p, C.POINTER(FlowParams)] + [C.c_void_p] * 7 + [C.POINTER(FlowStats)]),
+    "ptv_flow_analysis_dev": (C.c_int, [C.c_void_p, C.POINTER(FlowParams)] + [C.c_void_p] * 8 +
+                              [C.POINTER(FlowStats)]),
+    "ptv_flow_derived": (C.c_int, [C.c_void_p, C.POINTER(FlowParams)] + [C.c_void_p] * 4 + [C.POINTER(FlowStats)]),
+    "ptv_flow_derived_dev": (C.c_int, [C.c_void_p, C.POINTER(FlowParams)] + [C.c_void_p] * 5 +
+                             [C.POINTER(FlowStats)]),
     "ptv_last_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     "ptv_debug_stamps": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double)]),
 }
@@ -328,6 +357,13 @@ def abi_sizes5():
     out = (C.c_int64 * 2)()
     check(lib().ptv_abi_sizes5(out))
     return list(out), [C.sizeof(VariationalParams), C.sizeof(VariationalStats)]
+
+
+def abi_sizes6():
+    """(C sizeof, ctypes sizeof) of ptv_flow_params and ptv_flow_stats."""
+    out = (C.c_int64 * 2)()
+    check(lib().ptv_abi_sizes6(out))
+    return list(out), [C.sizeof(FlowParams), C.sizeof(FlowStats)]
 
 
 class Triangulation:
@@ -906,3 +942,76 @@ class Context:
         d = np.empty_like(f[0])
         check(lib().ptv_divergence_operator_apply(self.h, C.byref(prm), *[as_dp(a) for a in f], as_dp(d)))
         return d
+
+    # -- flow analysis (velocity_analysis.py:10-188) ------------------------
+    def flow_analysis(self, u, v, w, dx, dy, dz, viscosity=0.0, fluid_mask=None, outputs=FLOW_OUTPUTS,
+                      spacing_strong=False, z_range=None, edges=(True, True)):
+        """One stencil pass over float32 / float64 (nz, ny, nx) host fields of one dtype.  Returns
+        ``(fields, stats)``: a dict with the requested ``outputs`` (names of FLOW_OUTPUTS), each
+        (z1 - z0, ny, nx) of the fields' dtype, and the statistics dict.  ``spacing_strong``: numpy's
+        division rule for float32 fields (np.float64 spacings); ``z_range`` / ``edges`` as
+        ``divergence``."""
+        ft = u.dtype
+        f = [np.ascontiguousarray(a, dtype=ft) for a in (u, v, w)]
+        nz, ny, nx = f[0].shape
+        mk = None
+        if fluid_mask is not None:
+            mk = np.ascontiguousarray(fluid_mask, dtype=bool).view(np.uint8).reshape(nz, ny, nx)
+        z0, z1 = (0, nz) if z_range is None else z_range
+        prm = FlowParams(nx, ny, nz, z0, z1, int(bool(edges[0])), int(bool(edges[1])),
+                         F32 if ft == np.float32 else F64, int(bool(spacing_strong)), float(dx), float(dy),
+                         float(dz), float(viscosity), mk.ctypes.data_as(_u8p) if mk is not None else None)
+        out = {name: np.empty((max(z1 - z0, 0), ny, nx), dtype=ft) for name in FLOW_OUTPUTS if name in outputs}
+        st = FlowStats()
+        check(lib().ptv_flow_analysis(self.h, C.byref(prm), *[a.ctypes.data_as(C.c_void_p) for a in f],
+                                      *[out[n].ctypes.data_as(C.c_void_p) if n in out else None
+                                        for n in FLOW_OUTPUTS], C.byref(st)))
+        return out, st.as_dict()
+
+    def flow_analysis_dev(self, nx, ny, nz, ptrs, out_ptrs, dx, dy, dz, viscosity=0.0, mask_ptr=0, field_dtype=F64,
+                          spacing_strong=False, z_range=None, edges=(True, True), stream=0):
+        """Device-pointer flow analysis (fields, mask and outputs resident in HBM).  ``out_ptrs``: four
+        device pointers in FLOW_OUTPUTS order, 0 = not computed.  Returns the statistics dict."""
+        z0, z1 = (0, nz) if z_range is None else z_range
+        prm = FlowParams(nx, ny, nz, z0, z1, int(bool(edges[0])), int(bool(edges[1])), int(field_dtype),
+                         int(bool(spacing_strong)), float(dx), float(dy), float(dz), float(viscosity),
+                         C.cast(C.c_void_p(mask_ptr), _u8p) if mask_ptr else None)
+        st = FlowStats()
+        check(lib().ptv_flow_analysis_dev(self.h, C.byref(prm), *[C.c_void_p(p) for p in ptrs],
+                                          *[C.c_void_p(p) if p else None for p in out_ptrs],
+                                          C.c_void_p(stream or 0), C.byref(st)))
+        return st.as_dict()
+
+    def flow_derived(self, strain_rate, vorticity_mag=None, viscosity=0.0, fluid_mask=None,
+                     outputs=("dissipation", "flow_type")):
+        """The elementwise mode: dissipation and / or flow type of host S (and O) arrays of one
+        float32 / float64 dtype and any one shape.  Returns ``(fields, stats)`` as flow_analysis."""
+        ft = strain_rate.dtype
+        s = np.ascontiguousarray(strain_rate, dtype=ft)
+        o = np.ascontiguousarray(vorticity_mag, dtype=ft) if "flow_type" in outputs else None
+        mk = None
+        if fluid_mask is not None:
+            mk = np.ascontiguousarray(fluid_mask, dtype=bool).view(np.uint8)
+        nx, ny, nz = s.shape[::-1] if s.ndim == 3 else (s.size, 1, 1)
+        prm = FlowParams(nx, ny, nz, 0, nz, 1, 1, F32 if ft == np.float32 else F64, 0, 1.0, 1.0, 1.0,
+                         float(viscosity), mk.ctypes.data_as(_u8p) if mk is not None else None)
+        out = {name: np.empty(s.shape, dtype=ft) for name in ("dissipation", "flow_type") if name in outputs}
+        st = FlowStats()
+        check(lib().ptv_flow_derived(self.h, C.byref(prm), s.ctypes.data_as(C.c_void_p),
+                                     o.ctypes.data_as(C.c_void_p) if o is not None else None,
+                                     *[out[n].ctypes.data_as(C.c_void_p) if n in out else None
+                                       for n in ("dissipation", "flow_type")], C.byref(st)))
+        return out, st.as_dict()
+
+    def flow_derived_dev(self, n, strain_ptr, vorticity_ptr, dissipation_ptr, flow_type_ptr, viscosity=0.0,
+                         mask_ptr=0, field_dtype=F64, stream=0):
+        """Device-pointer elementwise mode over ``n`` voxels; a 0 output pointer = not computed."""
+        prm = FlowParams(int(n), 1, 1, 0, 1, 1, 1, int(field_dtype), 0, 1.0, 1.0, 1.0, float(viscosity),
+                         C.cast(C.c_void_p(mask_ptr), _u8p) if mask_ptr else None)
+        st = FlowStats()
+        check(lib().ptv_flow_derived_dev(self.h, C.byref(prm), C.c_void_p(strain_ptr),
+                                         C.c_void_p(vorticity_ptr) if vorticity_ptr else None,
+                                         C.c_void_p(dissipation_ptr) if dissipation_ptr else None,
+                                         C.c_void_p(flow_type_ptr) if flow_type_ptr else None,
+                                         C.c_void_p(stream or 0), C.byref(st)))
+        return st.as_dict()

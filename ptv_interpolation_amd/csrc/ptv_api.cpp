@@ -86,6 +86,16 @@ int ptv_abi_sizes5(int64_t out2[2]) {
     return PTV_OK;
 }
 
+int ptv_abi_sizes6(int64_t out2[2]) {
+    if (!out2) {
+        set_error("ptv_abi_sizes6: out is NULL");
+        return PTV_E_ARG;
+    }
+    out2[0] = (int64_t)sizeof(ptv_flow_params);
+    out2[1] = (int64_t)sizeof(ptv_flow_stats);
+    return PTV_OK;
+}
+
 const char *ptv_last_error(void) { return g_last_error.c_str(); }
 
 int ptv_device_count(int *out) {
@@ -921,6 +931,212 @@ int ptv_variational_apply(ptv_ctx *c, const ptv_variational_params *prm, const d
     double *dst[3] = {yu, yv, yw};
     for (int i = 0; i < 3; ++i) PTV_HIP(hipMemcpyAsync(dst[i], f[3 + i], n * sizeof(double), hipMemcpyDeviceToHost, s));
     PTV_HIP(hipStreamSynchronize(s));
+    return PTV_OK;
+}
+
+// ---- flow analysis (ptv_flow.hip) ----
+// ptv_flow_params -> FlowArgs, with the same checks for the host and device calls; the elementwise
+// mode (stencil = false) reads neither the slab nor the spacings.
+static int flow_args(ptv_ctx *c, const ptv_flow_params *prm, bool stencil, FlowArgs &a) {
+    if (!c || !prm) {
+        set_error("NULL context/params");
+        return PTV_E_ARG;
+    }
+    if (prm->field_dtype != PTV_F64 && prm->field_dtype != PTV_F32) {
+        set_error("flow analysis: field_dtype must be PTV_F64 or PTV_F32");
+        return PTV_E_ARG;
+    }
+    const int64_t least = stencil ? 2 : 1, most = 1 << 30;
+    if (prm->nx < least || prm->ny < least || prm->nz < least) {
+        set_error(stencil ? "Shape of array too small to calculate a numerical gradient, at least (edge_order + 1) "
+                            "elements are required."
+                          : "flow derived: dimensions must be positive");
+        return PTV_E_ARG;
+    }
+    if (prm->nx > most || prm->ny > most || prm->nz > most ||
+        (double)prm->nx * (double)prm->ny * (double)prm->nz >= 1099511627776.0) {
+        set_error("flow analysis: fewer than 2^40 voxels, at most 2^30 per axis");
+        return PTV_E_ARG;
+    }
+    a = FlowArgs{};
+    a.nx = (int)prm->nx;
+    a.ny = (int)prm->ny;
+    a.nz = (int)prm->nz;
+    a.field_f32 = prm->field_dtype == PTV_F32;
+    a.strong = prm->spacing_strong ? 1 : 0;
+    a.viscosity = prm->viscosity;
+    if (stencil) {
+        const int64_t lo = prm->edge_lo ? 0 : 1, hi = prm->nz - (prm->edge_hi ? 0 : 1);
+        if (prm->z_begin < lo || prm->z_end > hi || prm->z_begin > prm->z_end) {
+            set_error("flow analysis: planes [" + std::to_string(prm->z_begin) + ", " + std::to_string(prm->z_end) +
+                      ") must lie in [" + std::to_string(lo) + ", " + std::to_string(hi) +
+                      ") (a non-edge buffer end is a halo plane)");
+            return PTV_E_ARG;
+        }
+        for (double h : {prm->dx, prm->dy, prm->dz})
+            if (!(h > 0.0) || !std::isfinite(h)) {
+                set_error("flow analysis: spacings must be positive and finite");
+                return PTV_E_ARG;
+            }
+        a.z_begin = (int)prm->z_begin;
+        a.z_end = (int)prm->z_end;
+        a.edge_lo = prm->edge_lo ? 1 : 0;
+        a.edge_hi = prm->edge_hi ? 1 : 0;
+        a.dx = prm->dx;
+        a.dy = prm->dy;
+        a.dz = prm->dz;
+    }
+    PTV_HIP(hipSetDevice(c->device));
+    return PTV_OK;
+}
+
+// the reduced rows -> ptv_flow_stats (synchronises `s`)
+static int flow_finish(ptv_ctx *c, unsigned want, int64_t nvox, hipStream_t s, ptv_flow_stats *st) {
+    double h[kFlowRows];
+    PTV_HIP(hipMemcpyAsync(h, c->flow_res.p, sizeof(h), hipMemcpyDeviceToHost, s));
+    PTV_HIP(hipStreamSynchronize(s));
+    float ms = 0.f;
+    PTV_HIP(hipEventElapsedTime(&ms, c->ev_flow0, c->ev_flow1));
+    if (!st) return PTV_OK;
+    *st = ptv_flow_stats{};
+    st->n_voxels = nvox;
+    st->n_fluid = (int64_t)h[15];
+    st->sum_u = h[0];
+    st->sum_v = h[1];
+    st->sum_w = h[2];
+    for (int k = 0; k < 4; ++k) {
+        if (!(want >> k & 1)) continue;
+        st->sum[k] = st->sum_fluid[k] = h[3 + 3 * k];
+        st->max[k] = h[4 + 3 * k];
+        st->min[k] = h[5 + 3 * k];
+    }
+    st->ms_stencil = ms;
+    return PTV_OK;
+}
+
+static int run_flow(ptv_ctx *c, const FlowArgs &a, const void *U, const void *V, const void *W, const uint8_t *M,
+                    void *const out[4], hipStream_t s) {
+    PTV_TRY(c->flow_part.ensure(flow_partials(a)));
+    PTV_TRY(c->flow_res.ensure(kFlowRows));
+    PTV_TRY(c->ev_flow0.record(s));
+    PTV_TRY(launch_flow(a, U, V, W, M, out, c->flow_part.p, c->flow_res.p, s));
+    PTV_TRY(c->ev_flow1.record(s));
+    return PTV_OK;
+}
+
+static unsigned flow_want(void *const out[4]) {
+    return (out[0] ? 1u : 0u) | (out[1] ? 2u : 0u) | (out[2] ? 4u : 0u) | (out[3] ? 8u : 0u);
+}
+
+int ptv_flow_analysis_dev(ptv_ctx *c, const ptv_flow_params *prm, const void *U, const void *V, const void *W,
+                          void *strain, void *dissipation, void *vorticity, void *flow_type, void *stream,
+                          ptv_flow_stats *st) {
+    FlowArgs a{};
+    PTV_TRY(flow_args(c, prm, true, a));
+    if (!U || !V || !W) {
+        set_error("flow analysis: NULL field");
+        return PTV_E_ARG;
+    }
+    if (st) *st = ptv_flow_stats{};
+    if (a.z_end <= a.z_begin) return PTV_OK;
+    void *const out[4] = {strain, dissipation, vorticity, flow_type};
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    PTV_TRY(run_flow(c, a, U, V, W, prm->fluid_mask, out, s));
+    return flow_finish(c, flow_want(out), (prm->z_end - prm->z_begin) * prm->nx * prm->ny, s, st);
+}
+
+int ptv_flow_analysis(ptv_ctx *c, const ptv_flow_params *prm, const void *U, const void *V, const void *W,
+                      void *strain, void *dissipation, void *vorticity, void *flow_type, ptv_flow_stats *st) {
+    FlowArgs a{};
+    PTV_TRY(flow_args(c, prm, true, a));
+    if (!U || !V || !W) {
+        set_error("flow analysis: NULL field");
+        return PTV_E_ARG;
+    }
+    if (st) *st = ptv_flow_stats{};
+    if (a.z_end <= a.z_begin) return PTV_OK;
+    hipStream_t s = c->stream;
+    const size_t ts = a.field_f32 ? 4 : 8;
+    const int64_t nfull = prm->nz * prm->nx * prm->ny;
+    const int64_t nout = (prm->z_end - prm->z_begin) * prm->nx * prm->ny;
+    const void *src[3] = {U, V, W};
+    for (int i = 0; i < 3; ++i) {
+        PTV_TRY(c->flow_fld[i].ensure(nfull * ts));
+        PTV_HIP(hipMemcpyAsync(c->flow_fld[i].p, src[i], nfull * ts, hipMemcpyHostToDevice, s));
+    }
+    const uint8_t *M = nullptr;
+    if (prm->fluid_mask) {
+        PTV_TRY(c->mask.ensure(nfull));
+        PTV_HIP(hipMemcpyAsync(c->mask.p, prm->fluid_mask, nfull, hipMemcpyHostToDevice, s));
+        M = c->mask.p;
+    }
+    void *const host[4] = {strain, dissipation, vorticity, flow_type};
+    void *out[4] = {nullptr, nullptr, nullptr, nullptr};
+    for (int k = 0; k < 4; ++k) {
+        if (!host[k]) continue;
+        PTV_TRY(c->flow_out[k].ensure(nout * ts));
+        out[k] = c->flow_out[k].p;
+    }
+    PTV_TRY(run_flow(c, a, c->flow_fld[0].p, c->flow_fld[1].p, c->flow_fld[2].p, M, out, s));
+    for (int k = 0; k < 4; ++k)
+        if (host[k]) PTV_HIP(hipMemcpyAsync(host[k], out[k], nout * ts, hipMemcpyDeviceToHost, s));
+    return flow_finish(c, flow_want(out), nout, s, st);
+}
+
+int ptv_flow_derived_dev(ptv_ctx *c, const ptv_flow_params *prm, const void *strain, const void *vorticity_mag,
+                         void *dissipation, void *flow_type, void *stream, ptv_flow_stats *st) {
+    FlowArgs a{};
+    PTV_TRY(flow_args(c, prm, false, a));
+    if (!strain || (flow_type && !vorticity_mag)) {
+        set_error("flow derived: NULL strain rate, or flow type without the vorticity magnitude");
+        return PTV_E_ARG;
+    }
+    if (st) *st = ptv_flow_stats{};
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    const int64_t n = prm->nz * prm->nx * prm->ny;
+    PTV_TRY(c->flow_part.ensure(flow_derived_partials(n)));
+    PTV_TRY(c->flow_res.ensure(kFlowRows));
+    PTV_TRY(c->ev_flow0.record(s));
+    PTV_TRY(launch_flow_derived(a, n, strain, vorticity_mag, prm->fluid_mask, dissipation, flow_type, c->flow_part.p,
+                                c->flow_res.p, s));
+    PTV_TRY(c->ev_flow1.record(s));
+    return flow_finish(c, (dissipation ? 2u : 0u) | (flow_type ? 8u : 0u), n, s, st);
+}
+
+int ptv_flow_derived(ptv_ctx *c, const ptv_flow_params *prm, const void *strain, const void *vorticity_mag,
+                     void *dissipation, void *flow_type, ptv_flow_stats *st) {
+    FlowArgs a{};
+    PTV_TRY(flow_args(c, prm, false, a));
+    if (!strain || (flow_type && !vorticity_mag)) {
+        set_error("flow derived: NULL strain rate, or flow type without the vorticity magnitude");
+        return PTV_E_ARG;
+    }
+    hipStream_t s = c->stream;
+    const size_t ts = a.field_f32 ? 4 : 8;
+    const int64_t n = prm->nz * prm->nx * prm->ny;
+    const void *src[2] = {strain, flow_type ? vorticity_mag : nullptr};
+    for (int i = 0; i < 2; ++i) {
+        if (!src[i]) continue;
+        PTV_TRY(c->flow_fld[i].ensure(n * ts));
+        PTV_HIP(hipMemcpyAsync(c->flow_fld[i].p, src[i], n * ts, hipMemcpyHostToDevice, s));
+    }
+    ptv_flow_params dp = *prm;
+    dp.fluid_mask = nullptr;
+    if (prm->fluid_mask) {
+        PTV_TRY(c->mask.ensure(n));
+        PTV_HIP(hipMemcpyAsync(c->mask.p, prm->fluid_mask, n, hipMemcpyHostToDevice, s));
+        dp.fluid_mask = c->mask.p;
+    }
+    void *const host[2] = {dissipation, flow_type};
+    void *out[2] = {nullptr, nullptr};
+    for (int k = 0; k < 2; ++k) {
+        if (!host[k]) continue;
+        PTV_TRY(c->flow_out[k].ensure(n * ts));
+        out[k] = c->flow_out[k].p;
+    }
+    PTV_TRY(ptv_flow_derived_dev(c, &dp, c->flow_fld[0].p, src[1] ? c->flow_fld[1].p : nullptr, out[0], out[1], s, st));
+    for (int k = 0; k < 2; ++k)
+        if (host[k]) PTV_HIP(hipMemcpy(host[k], out[k], n * ts, hipMemcpyDeviceToHost));
     return PTV_OK;
 }
 

@@ -97,6 +97,9 @@ struct ptv_ctx {
     ptv::DevBuf<double> clean_fld[4];                                 // its host calls: U, V, W (in place), phi / x
     ptv::VarWork var;                                                 // variational cleaning: CG vectors, state
     ptv::DevBuf<double> var_fld[6];                                   // its host calls: fields (in place) / x, y
+    ptv::DevBuf<double> flow_part, flow_res;                          // flow analysis: per-block partials, reduced rows
+    ptv::DevBuf<uint8_t> flow_fld[3], flow_out[4];                   // its host calls: inputs (U, V, W | S, O), outputs
+    ptv::Event ev_flow0, ev_flow1;                                    // around its kernels
     ptv::PinnedBuf<double> h_bbox;                                    // pinned, kHostWords doubles
     ptv::PinnedBuf<unsigned long long> h_misc;  // pinned scratch words (cull count, halo bound, repair count)
     ptv_stats last{};

@@ -202,6 +202,32 @@ struct DivArgs {
 int launch_divergence(const DivArgs &a, const void *U, const void *V, const void *W, const uint8_t *M, void *out,
                       hipStream_t s);
 
+// ---- flow analysis (ptv_flow.hip) ----
+// Rows of the per-block partials and of the reduced result: 0-2 the sums of u, v, w; 3 + 3k, 4 + 3k,
+// 5 + 3k the sum, max and min of output k (0 strain, 1 dissipation, 2 vorticity, 3 flow type); 15 the
+// fluid voxel count.
+constexpr int kFlowRows = 16;
+struct FlowArgs {
+    int nx, ny, nz;          // buffer shape (nz planes, C order)
+    int z_begin, z_end;      // buffer planes computed (output plane 0 = z_begin)
+    int edge_lo, edge_hi;    // buffer plane 0 / nz-1 is a domain z face (else a halo plane)
+    int field_f32;           // fields and outputs are float32 (else float64)
+    int strong;              // float32 fields: divide in float64 and round (np.float64 spacings)
+    double dx, dy, dz;
+    double viscosity;
+    int ntx = 0, nty = 0, ntiles = 0, npart = 0;  // tile and partial counts (set by the launcher)
+    int xcd = 1;                                  // XCD-contiguous tile order
+};
+// doubles of `part` a launch needs; `res` holds kFlowRows doubles
+size_t flow_partials(const FlowArgs &a);
+size_t flow_derived_partials(int64_t n);
+// out[k]: output k (order above) or NULL = not computed; M may be NULL (every voxel fluid)
+int launch_flow(const FlowArgs &a, const void *U, const void *V, const void *W, const uint8_t *M, void *const out[4],
+                double *part, double *res, hipStream_t s);
+// dissipation (oD) and / or flow type (oF, needs O) of n voxels from S and O
+int launch_flow_derived(const FlowArgs &a, int64_t n, const void *S, const void *O, const uint8_t *M, void *oD,
+                        void *oF, double *part, double *res, hipStream_t s);
+
 // ---- linear (ptv_linear.hip): griddata(method='linear') over scipy's Delaunay triangulation ----
 struct LinearKernelArgs {
     int nx, ny;          // grid plane
