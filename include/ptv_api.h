@@ -374,6 +374,40 @@ typedef struct {
     double ms_stencil;               /* the kernels of the call, hipEvent based */
 } ptv_flow_stats;
 
+/*
+ * Staircase interface drag (velocity_analysis.compute_interface_drag, method='staircase',
+ * velocity_analysis.py:332-511) and the gradient sums of compute_permeability_from_pressure
+ * (:659-697).  The int32 label mask (0 = fluid, a positive label = a phase), the fields u, v, w and
+ * the optional pressure are (nz, ny, nx) C order; the fields share field_dtype.  Along every axis
+ * each pair of adjacent voxels (curr, next) is a face of label L in direction A when curr == 0 and
+ * next == L, in direction B when curr == L and next == 0; faces between two labels, faces that
+ * touch a negative value or a label not in the table, and pairs across an array edge give nothing.
+ * Per face, in float64 (float32 fields are widened on load), as the reference writes them:
+ *     pressure term  (0.5 * (p[curr] + p[next])) * area in direction A, its negation * area in B
+ *     d = (-2.0 * vel[fluid cell]) / step
+ *     viscous term   ((viscosity * 2) * d) * area along the face normal, (viscosity * d) * area else
+ * with area = dy*dx, dz*dx, dz*dy and step = dz, dy, dx for axes 0 (z), 1 (y), 2 (x).
+ * PTV_API_VERSION is not raised: the presence of ptv_abi_sizes7 is the capability probe.
+ */
+typedef struct {
+    int64_t nx, ny, nz;    /* positive; an axis of length 1 has no faces */
+    int field_dtype;       /* PTV_F64 | PTV_F32 */
+    int n_labels;          /* >= 1 */
+    double dx, dy, dz;     /* positive and finite */
+    double viscosity;      /* finite */
+    const int32_t *labels; /* n_labels positive labels, strictly ascending; HOST memory in both calls */
+} ptv_drag_params;
+
+/* One record per (label, axis, direction): records[(l * 3 + axis) * 2 + dir], dir 0 = A, 1 = B.
+ * sum_u, sum_v, sum_w are the sums of the viscous terms of the three velocity components (the one
+ * along the axis carries the factor 2); sum_p is 0 without a pressure field.  Sums are float64
+ * whatever the field dtype, the same bits on every call and independent of which other labels the
+ * table holds alongside (fixed order, no atomics). */
+typedef struct {
+    int64_t count;                     /* faces */
+    double sum_p, sum_u, sum_v, sum_w;
+} ptv_drag_stats;
+
 /* Library / device management. */
 int ptv_version(void);
 /* sizeof(ptv_particles, ptv_grid, ptv_knn_params, ptv_stats, ptv_rbf_params, ptv_div_params):
@@ -391,6 +425,9 @@ int ptv_abi_sizes5(int64_t out2[2]);
 /* sizeof(ptv_flow_params, ptv_flow_stats): the same self-check.  A library that has this symbol has
  * the flow analysis entry points (PTV_API_VERSION stays 11). */
 int ptv_abi_sizes6(int64_t out2[2]);
+/* sizeof(ptv_drag_params, ptv_drag_stats): the same self-check.  A library that has this symbol has
+ * the interface drag and gradient sums entry points (PTV_API_VERSION stays 11). */
+int ptv_abi_sizes7(int64_t out2[2]);
 const char *ptv_last_error(void);
 int ptv_device_count(int *out);
 int ptv_init(int device, ptv_ctx **out);
@@ -597,6 +634,34 @@ int ptv_flow_derived(ptv_ctx *ctx, const ptv_flow_params *prm, const void *strai
 
 int ptv_flow_derived_dev(ptv_ctx *ctx, const ptv_flow_params *prm, const void *strain, const void *vorticity_mag,
                          void *dissipation, void *flow_type, void *stream, ptv_flow_stats *st);
+
+/*
+ * Interface drag, host buffers: H2D of the mask and the fields, one pass over the mask per 32
+ * labels, D2H of the records.  P may be NULL (no pressure read, sum_p = 0).  records: n_labels * 6
+ * entries, filled in the table's order.  ms (may be NULL) receives the kernels' time, hipEvent
+ * based.
+ */
+int ptv_interface_drag(ptv_ctx *ctx, const ptv_drag_params *prm, const int32_t *mask, const void *U, const void *V,
+                       const void *W, const void *P, ptv_drag_stats *records, double *ms);
+
+/* Same on device pointers (mask, fields; prm->labels and records stay host memory), enqueued on
+ * `stream` (NULL = the ctx's own); synchronises (the records are returned). */
+int ptv_interface_drag_dev(ptv_ctx *ctx, const ptv_drag_params *prm, const int32_t *mask, const void *U,
+                           const void *V, const void *W, const void *P, void *stream, ptv_drag_stats *records,
+                           double *ms);
+
+/*
+ * sums3 = the float64 sums over the whole volume of the three components of
+ * np.gradient(P, dz, dy, dx), in that order: central differences inside, one-sided at the two ends,
+ * each quotient in the field dtype under numpy's division rule (prm->spacing_strong, as for the
+ * flow analysis) before it is widened and added, in a fixed order.  Reads nx, ny, nz, field_dtype,
+ * spacing_strong and the spacings of prm; the plane range must be the whole buffer.  An axis
+ * shorter than 2 returns PTV_E_ARG (np.gradient raises ValueError).  Host buffer.
+ */
+int ptv_gradient_sums(ptv_ctx *ctx, const ptv_flow_params *prm, const void *P, double sums3[3]);
+
+/* Same on a device pointer, enqueued on `stream` (NULL = the ctx's own); synchronises. */
+int ptv_gradient_sums_dev(ptv_ctx *ctx, const ptv_flow_params *prm, const void *P, void *stream, double sums3[3]);
 
 /*
  * Last-launch k-NN kernel duration in ms (hipEvent pair recorded around the

@@ -163,6 +163,22 @@ class FlowStats(C.Structure):
         return d
 
 
+class DragParams(C.Structure):
+    _fields_ = [("nx", C.c_int64), ("ny", C.c_int64), ("nz", C.c_int64), ("field_dtype", C.c_int),
+                ("n_labels", C.c_int), ("dx", C.c_double), ("dy", C.c_double), ("dz", C.c_double),
+                ("viscosity", C.c_double), ("labels", C.POINTER(C.c_int32))]
+
+
+class DragStats(C.Structure):
+    """One (label, axis, direction) record of the interface drag."""
+    _fields_ = [("count", C.c_int64), ("sum_p", C.c_double), ("sum_u", C.c_double), ("sum_v", C.c_double),
+                ("sum_w", C.c_double)]
+
+
+# the records as a numpy array: (n_labels, 3 axes, 2 directions) of this dtype
+DRAG_RECORD = np.dtype([("count", np.int64), ("sum_p", np.float64), ("sum_u", np.float64), ("sum_v", np.float64),
+                        ("sum_w", np.float64)])
+
 MASK_BOOL = 0
 MASK_BITS = 1
 
@@ -255,6 +271,11 @@ EXPORTS = {
     "ptv_flow_derived": (C.c_int, [C.c_void_p, C.POINTER(FlowParams)] + [C.c_void_p] * 4 + [C.POINTER(FlowStats)]),
     "ptv_flow_derived_dev": (C.c_int, [C.c_void_p, C.POINTER(FlowParams)] + [C.c_void_p] * 5 +
                              [C.POINTER(FlowStats)]),
+    "ptv_abi_sizes7": (C.c_int, [C.POINTER(C.c_int64)]),
+    "ptv_interface_drag": (C.c_int, [C.c_void_p, C.POINTER(DragParams)] + [C.c_void_p] * 6 + [_dp]),
+    "ptv_interface_drag_dev": (C.c_int, [C.c_void_p, C.POINTER(DragParams)] + [C.c_void_p] * 7 + [_dp]),
+    "ptv_gradient_sums": (C.c_int, [C.c_void_p, C.POINTER(FlowParams), C.c_void_p, _dp]),
+    "ptv_gradient_sums_dev": (C.c_int, [C.c_void_p, C.POINTER(FlowParams), C.c_void_p, C.c_void_p, _dp]),
     "ptv_last_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     "ptv_debug_stamps": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double)]),
 }
@@ -364,6 +385,30 @@ def abi_sizes6():
     out = (C.c_int64 * 2)()
     check(lib().ptv_abi_sizes6(out))
     return list(out), [C.sizeof(FlowParams), C.sizeof(FlowStats)]
+
+
+def abi_sizes7():
+    """(C sizeof, ctypes sizeof) of ptv_drag_params and ptv_drag_stats."""
+    out = (C.c_int64 * 2)()
+    check(lib().ptv_abi_sizes7(out))
+    return list(out), [C.sizeof(DragParams), C.sizeof(DragStats)]
+
+
+def drag_label_table(labels):
+    """The sorted unique int32 table the device takes and, per given label, its slot in it.  The
+    labels must be positive integers of the int32 range (``NotImplementedError`` otherwise)."""
+    lab = np.asarray(labels)
+    if lab.ndim != 1 or lab.size == 0:
+        raise ValueError("labels must be a non-empty 1-D sequence")
+    if lab.dtype.kind not in "biu":
+        raise NotImplementedError(f"labels of dtype {lab.dtype} (GPU path: integers or bool)")
+    lab = lab.astype(np.int64) if lab.dtype != np.uint64 else lab
+    if lab.max() > np.iinfo(np.int32).max or lab.min() < np.iinfo(np.int32).min:
+        raise NotImplementedError("labels outside the int32 range are not supported on the GPU path")
+    if lab.min() <= 0:
+        raise NotImplementedError("labels must be positive on the GPU path (0 is the fluid)")
+    table, slot = np.unique(lab.astype(np.int32), return_inverse=True)
+    return np.ascontiguousarray(table), slot.reshape(-1)
 
 
 class Triangulation:
@@ -1015,3 +1060,56 @@ class Context:
                                          C.c_void_p(flow_type_ptr) if flow_type_ptr else None,
                                          C.c_void_p(stream or 0), C.byref(st)))
         return st.as_dict()
+
+    # -- interface drag, gradient sums (velocity_analysis.py:332-511, :659-697) ----
+    def _drag_call(self, fn, shape, ptrs, labels, dx, dy, dz, viscosity, field_dtype, extra=()):
+        table, slot = drag_label_table(labels)
+        nz, ny, nx = shape
+        prm = DragParams(nx, ny, nz, int(field_dtype), int(table.size), float(dx), float(dy), float(dz),
+                         float(viscosity), table.ctypes.data_as(C.POINTER(C.c_int32)))
+        rec = np.zeros((table.size, 3, 2), dtype=DRAG_RECORD)
+        ms = C.c_double(0.0)
+        check(fn(self.h, C.byref(prm), *[C.c_void_p(p) if p else None for p in ptrs], *extra,
+                 rec.ctypes.data_as(C.c_void_p), C.byref(ms)))
+        return rec[slot], ms.value
+
+    def interface_drag(self, mask, u, v, w, pressure, viscosity, dx, dy, dz, labels):
+        """Staircase interface drag of host arrays: an integer / bool label ``mask`` (nz, ny, nx), the
+        fields (one float32 / float64 dtype; ``pressure`` may be None).  ``labels``: positive
+        integers in any order, repeats allowed.  Returns ``(records, ms)``: a (len(labels), 3, 2)
+        array of DRAG_RECORD, one per given label, axis (0 = z, 1 = y, 2 = x) and direction (0 = A,
+        fluid -> label; 1 = B), and the kernels' time."""
+        ft = u.dtype
+        mk = np.ascontiguousarray(mask, dtype=np.int32)
+        f = [np.ascontiguousarray(a, dtype=ft) for a in (u, v, w)]
+        if pressure is not None:
+            f.append(np.ascontiguousarray(pressure, dtype=ft))
+        ptrs = [mk.ctypes.data] + [a.ctypes.data for a in f] + [0] * (4 - len(f))
+        return self._drag_call(lib().ptv_interface_drag, mk.shape, ptrs, labels, dx, dy, dz, viscosity,
+                               F32 if ft == np.float32 else F64)
+
+    def interface_drag_dev(self, nx, ny, nz, mask_ptr, ptrs, pressure_ptr, viscosity, dx, dy, dz, labels,
+                           field_dtype=F64, stream=0):
+        """Device-pointer interface drag: an int32 mask, u, v, w (``ptrs``) and the pressure (0 = none)
+        resident in HBM; the labels and the records stay on the host.  Returns as interface_drag."""
+        return self._drag_call(lib().ptv_interface_drag_dev, (nz, ny, nx), [mask_ptr, *ptrs, pressure_ptr], labels,
+                               dx, dy, dz, viscosity, field_dtype, extra=(C.c_void_p(stream or 0),))
+
+    def gradient_sums(self, pressure, dx, dy, dz, spacing_strong=False):
+        """The float64 sums over the volume of ``np.gradient(pressure, dz, dy, dx)``'s three components,
+        in that order, for a host float32 / float64 (nz, ny, nx) array."""
+        p = np.ascontiguousarray(pressure)
+        nz, ny, nx = p.shape
+        prm = FlowParams(nx, ny, nz, 0, nz, 1, 1, F32 if p.dtype == np.float32 else F64, int(bool(spacing_strong)),
+                         float(dx), float(dy), float(dz), 0.0, None)
+        out = (C.c_double * 3)()
+        check(lib().ptv_gradient_sums(self.h, C.byref(prm), p.ctypes.data_as(C.c_void_p), out))
+        return [float(x) for x in out]
+
+    def gradient_sums_dev(self, nx, ny, nz, ptr, dx, dy, dz, field_dtype=F64, spacing_strong=False, stream=0):
+        """The same for a field resident in HBM."""
+        prm = FlowParams(nx, ny, nz, 0, nz, 1, 1, int(field_dtype), int(bool(spacing_strong)), float(dx), float(dy),
+                         float(dz), 0.0, None)
+        out = (C.c_double * 3)()
+        check(lib().ptv_gradient_sums_dev(self.h, C.byref(prm), C.c_void_p(ptr), C.c_void_p(stream or 0), out))
+        return [float(x) for x in out]

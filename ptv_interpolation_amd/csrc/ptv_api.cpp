@@ -96,6 +96,16 @@ int ptv_abi_sizes6(int64_t out2[2]) {
     return PTV_OK;
 }
 
+int ptv_abi_sizes7(int64_t out2[2]) {
+    if (!out2) {
+        set_error("ptv_abi_sizes7: out is NULL");
+        return PTV_E_ARG;
+    }
+    out2[0] = (int64_t)sizeof(ptv_drag_params);
+    out2[1] = (int64_t)sizeof(ptv_drag_stats);
+    return PTV_OK;
+}
+
 const char *ptv_last_error(void) { return g_last_error.c_str(); }
 
 int ptv_device_count(int *out) {
@@ -1138,6 +1148,177 @@ int ptv_flow_derived(ptv_ctx *c, const ptv_flow_params *prm, const void *strain,
     for (int k = 0; k < 2; ++k)
         if (host[k]) PTV_HIP(hipMemcpy(host[k], out[k], n * ts, hipMemcpyDeviceToHost));
     return PTV_OK;
+}
+
+// ---- interface drag and gradient sums (ptv_drag.hip) ----
+static int drag_dims(int64_t nx, int64_t ny, int64_t nz, int64_t least, const char *what) {
+    const int64_t most = 1 << 30;
+    if (nx < least || ny < least || nz < least) {
+        set_error(least == 2 ? "Shape of array too small to calculate a numerical gradient, at least (edge_order + 1) "
+                               "elements are required."
+                             : std::string(what) + ": dimensions must be positive");
+        return PTV_E_ARG;
+    }
+    if (nx > most || ny > most || nz > most || (double)nx * (double)ny * (double)nz >= 1099511627776.0) {
+        set_error(std::string(what) + ": fewer than 2^40 voxels, at most 2^30 per axis");
+        return PTV_E_ARG;
+    }
+    return PTV_OK;
+}
+
+// ptv_drag_params -> DragArgs, with the same checks for the host and device calls
+static int drag_args(ptv_ctx *c, const ptv_drag_params *prm, DragArgs &a) {
+    if (!c || !prm) {
+        set_error("NULL context/params");
+        return PTV_E_ARG;
+    }
+    if (prm->field_dtype != PTV_F64 && prm->field_dtype != PTV_F32) {
+        set_error("interface drag: field_dtype must be PTV_F64 or PTV_F32");
+        return PTV_E_ARG;
+    }
+    PTV_TRY(drag_dims(prm->nx, prm->ny, prm->nz, 1, "interface drag"));
+    for (double h : {prm->dx, prm->dy, prm->dz})
+        if (!(h > 0.0) || !std::isfinite(h)) {
+            set_error("interface drag: spacings must be positive and finite");
+            return PTV_E_ARG;
+        }
+    if (!std::isfinite(prm->viscosity)) {
+        set_error("interface drag: viscosity must be finite");
+        return PTV_E_ARG;
+    }
+    if (prm->n_labels < 1 || !prm->labels) {
+        set_error("interface drag: at least one label");
+        return PTV_E_ARG;
+    }
+    for (int i = 0; i < prm->n_labels; ++i)
+        if (prm->labels[i] <= 0 || (i > 0 && prm->labels[i] <= prm->labels[i - 1])) {
+            set_error("interface drag: labels must be positive and strictly ascending");
+            return PTV_E_ARG;
+        }
+    a = DragArgs{};
+    a.nx = (int)prm->nx;
+    a.ny = (int)prm->ny;
+    a.nz = (int)prm->nz;
+    a.field_f32 = prm->field_dtype == PTV_F32;
+    a.area[0] = prm->dy * prm->dx;
+    a.area[1] = prm->dz * prm->dx;
+    a.area[2] = prm->dz * prm->dy;
+    a.step[0] = prm->dz;
+    a.step[1] = prm->dy;
+    a.step[2] = prm->dx;
+    a.viscosity = prm->viscosity;
+    PTV_HIP(hipSetDevice(c->device));
+    return PTV_OK;
+}
+
+int ptv_interface_drag_dev(ptv_ctx *c, const ptv_drag_params *prm, const int32_t *mask, const void *U, const void *V,
+                           const void *W, const void *P, void *stream, ptv_drag_stats *records, double *ms) {
+    DragArgs a{};
+    PTV_TRY(drag_args(c, prm, a));
+    if (!mask || !U || !V || !W || !records) {
+        set_error("interface drag: NULL mask, field or records");
+        return PTV_E_ARG;
+    }
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    const int nl = prm->n_labels;
+    const size_t nrows = (size_t)nl * kDragSlotRows;
+    PTV_TRY(c->drag_part.ensure(drag_partials(a, nl)));
+    PTV_TRY(c->drag_res.ensure(nrows));
+    PTV_TRY(c->drag_labels.ensure((size_t)nl));
+    PTV_HIP(hipMemcpyAsync(c->drag_labels.p, prm->labels, (size_t)nl * sizeof(int), hipMemcpyHostToDevice, s));
+    PTV_TRY(c->ev_drag0.record(s));
+    PTV_TRY(launch_drag(a, mask, U, V, W, P, c->drag_labels.p, nl, c->drag_part.p, c->drag_res.p, s));
+    PTV_TRY(c->ev_drag1.record(s));
+    std::vector<double> h(nrows);
+    PTV_HIP(hipMemcpyAsync(h.data(), c->drag_res.p, nrows * sizeof(double), hipMemcpyDeviceToHost, s));
+    PTV_HIP(hipStreamSynchronize(s));
+    float t = 0.f;
+    PTV_HIP(hipEventElapsedTime(&t, c->ev_drag0, c->ev_drag1));
+    if (ms) *ms = t;
+    for (size_t r = 0; r < (size_t)nl * 6; ++r) {
+        const double *v = h.data() + r * kDragVals;
+        records[r] = ptv_drag_stats{(int64_t)v[0], v[1], v[2], v[3], v[4]};  // a count is an exact integer
+    }
+    return PTV_OK;
+}
+
+int ptv_interface_drag(ptv_ctx *c, const ptv_drag_params *prm, const int32_t *mask, const void *U, const void *V,
+                       const void *W, const void *P, ptv_drag_stats *records, double *ms) {
+    DragArgs a{};
+    PTV_TRY(drag_args(c, prm, a));
+    if (!mask || !U || !V || !W || !records) {
+        set_error("interface drag: NULL mask, field or records");
+        return PTV_E_ARG;
+    }
+    hipStream_t s = c->stream;
+    const size_t n = (size_t)(prm->nx * prm->ny * prm->nz), ts = a.field_f32 ? 4 : 8;
+    PTV_TRY(c->drag_mask.ensure(n));
+    PTV_HIP(hipMemcpyAsync(c->drag_mask.p, mask, n * sizeof(int), hipMemcpyHostToDevice, s));
+    const void *src[4] = {U, V, W, P};
+    for (int i = 0; i < 4; ++i) {
+        if (!src[i]) continue;
+        PTV_TRY(c->drag_fld[i].ensure(n * ts));
+        PTV_HIP(hipMemcpyAsync(c->drag_fld[i].p, src[i], n * ts, hipMemcpyHostToDevice, s));
+    }
+    return ptv_interface_drag_dev(c, prm, c->drag_mask.p, c->drag_fld[0].p, c->drag_fld[1].p, c->drag_fld[2].p,
+                                  P ? c->drag_fld[3].p : nullptr, s, records, ms);
+}
+
+int ptv_gradient_sums_dev(ptv_ctx *c, const ptv_flow_params *prm, const void *P, void *stream, double sums3[3]) {
+    if (!c || !prm || !P || !sums3) {
+        set_error("gradient sums: NULL argument");
+        return PTV_E_ARG;
+    }
+    if (prm->field_dtype != PTV_F64 && prm->field_dtype != PTV_F32) {
+        set_error("gradient sums: field_dtype must be PTV_F64 or PTV_F32");
+        return PTV_E_ARG;
+    }
+    PTV_TRY(drag_dims(prm->nx, prm->ny, prm->nz, 2, "gradient sums"));
+    if (prm->z_begin != 0 || prm->z_end != prm->nz || !prm->edge_lo || !prm->edge_hi) {
+        set_error("gradient sums: the plane range must be the whole buffer");
+        return PTV_E_UNSUPPORTED;
+    }
+    for (double h : {prm->dx, prm->dy, prm->dz})
+        if (!(h > 0.0) || !std::isfinite(h)) {
+            set_error("gradient sums: spacings must be positive and finite");
+            return PTV_E_ARG;
+        }
+    DragArgs a{};
+    a.nx = (int)prm->nx;
+    a.ny = (int)prm->ny;
+    a.nz = (int)prm->nz;
+    a.field_f32 = prm->field_dtype == PTV_F32;
+    a.strong = prm->spacing_strong ? 1 : 0;
+    a.step[0] = prm->dz;
+    a.step[1] = prm->dy;
+    a.step[2] = prm->dx;
+    PTV_HIP(hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    PTV_TRY(c->drag_part.ensure(drag_partials(a, 0)));
+    PTV_TRY(c->drag_res.ensure(3));
+    PTV_TRY(c->ev_drag0.record(s));
+    PTV_TRY(launch_gradient_sums(a, P, c->drag_part.p, c->drag_res.p, s));
+    PTV_TRY(c->ev_drag1.record(s));
+    PTV_HIP(hipMemcpyAsync(sums3, c->drag_res.p, 3 * sizeof(double), hipMemcpyDeviceToHost, s));
+    PTV_HIP(hipStreamSynchronize(s));
+    return PTV_OK;
+}
+
+int ptv_gradient_sums(ptv_ctx *c, const ptv_flow_params *prm, const void *P, double sums3[3]) {
+    if (!c || !prm || !P || !sums3) {
+        set_error("gradient sums: NULL argument");
+        return PTV_E_ARG;
+    }
+    if (prm->field_dtype != PTV_F64 && prm->field_dtype != PTV_F32) {
+        set_error("gradient sums: field_dtype must be PTV_F64 or PTV_F32");
+        return PTV_E_ARG;
+    }
+    PTV_TRY(drag_dims(prm->nx, prm->ny, prm->nz, 2, "gradient sums"));
+    PTV_HIP(hipSetDevice(c->device));
+    const size_t bytes = (size_t)(prm->nx * prm->ny * prm->nz) * (prm->field_dtype == PTV_F32 ? 4 : 8);
+    PTV_TRY(c->drag_fld[3].ensure(bytes));
+    PTV_HIP(hipMemcpyAsync(c->drag_fld[3].p, P, bytes, hipMemcpyHostToDevice, c->stream));
+    return ptv_gradient_sums_dev(c, prm, c->drag_fld[3].p, c->stream, sums3);
 }
 
 int ptv_last_stats(ptv_ctx *c, ptv_stats *st) {

@@ -100,6 +100,10 @@ struct ptv_ctx {
     ptv::DevBuf<double> flow_part, flow_res;                          // flow analysis: per-block partials, reduced rows
     ptv::DevBuf<uint8_t> flow_fld[3], flow_out[4];                   // its host calls: inputs (U, V, W | S, O), outputs
     ptv::Event ev_flow0, ev_flow1;                                    // around its kernels
+    ptv::DevBuf<double> drag_part, drag_res;                          // interface drag / gradient sums: partials, rows
+    ptv::DevBuf<int> drag_labels, drag_mask;                          // the label table; the mask of the host calls
+    ptv::DevBuf<uint8_t> drag_fld[4];                                 // the host calls' U, V, W, P
+    ptv::Event ev_drag0, ev_drag1;                                    // around its kernels
     ptv::PinnedBuf<double> h_bbox;                                    // pinned, kHostWords doubles
     ptv::PinnedBuf<unsigned long long> h_misc;  // pinned scratch words (cull count, halo bound, repair count)
     ptv_stats last{};

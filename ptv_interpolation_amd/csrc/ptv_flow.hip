@@ -37,6 +37,7 @@
 #include <type_traits>
 
 #include "../../include/ptv_api.h"
+#include "ptv_grad.hpp"
 #include "ptv_kernels.hpp"
 #include "ptv_wave.hpp"
 
@@ -92,16 +93,6 @@ __device__ __forceinline__ Vec<uint8_t, VEC> ldm(const uint8_t *p) {
         r.e[0] = p[0];
     }
     return r;
-}
-
-// the divisor's type: float64 for float64 fields and for the strong rule, else float32
-template <typename T, bool STRONG>
-using Div = std::conditional_t<std::is_same<T, double>::value || STRONG, double, float>;
-
-// (difference in T) / divisor under numpy's rule, rounded to T
-template <typename T, bool STRONG>
-__device__ __forceinline__ T quot(T d, Div<T, STRONG> h) {
-    return (T)((Div<T, STRONG>)d / h);
 }
 
 // np.max / np.min: a NaN on either side wins

@@ -228,6 +228,31 @@ int launch_flow(const FlowArgs &a, const void *U, const void *V, const void *W, 
 int launch_flow_derived(const FlowArgs &a, int64_t n, const void *S, const void *O, const uint8_t *M, void *oD,
                         void *oF, double *part, double *res, hipStream_t s);
 
+// ---- interface drag and gradient sums (ptv_drag.hip) ----
+// Rows of one (label slot, axis, direction): the face count, then the sums of the pressure, u, v and
+// w terms.  A label slot has 3 axes (0 = z, 1 = y, 2 = x) x 2 directions (A: fluid -> label, B:
+// label -> fluid) of them; the reduced result holds the slots in the label table's order.
+constexpr int kDragVals = 5;
+constexpr int kDragSlotRows = 3 * 2 * kDragVals;
+constexpr int kDragChunk = 32;  // label slots per pass (their per-wave rows fit the LDS)
+struct DragArgs {
+    int nx, ny, nz;          // mask and fields: (nz, ny, nx) C order
+    int field_f32;           // fields are float32 (else float64); all arithmetic is float64
+    int strong;              // gradient sums, float32: divide in float64 and round (np.float64 spacings)
+    double area[3], step[3]; // per axis 0, 1, 2: dy*dx, dz*dx, dz*dy and dz, dy, dx
+    double viscosity;
+    int64_t nvox = 0, span = 0;  // voxels; voxels per block (set by the launcher)
+    int items = 0;               // voxels per lane (set by the launcher)
+};
+// doubles of `part` a drag launch with nlabels labels needs (nlabels = 0: the gradient sums)
+size_t drag_partials(const DragArgs &a, int nlabels);
+// labels: nlabels ascending positive labels on the device; P may be NULL (pressure rows are 0);
+// res: nlabels * kDragSlotRows doubles
+int launch_drag(const DragArgs &a, const int *M, const void *U, const void *V, const void *W, const void *P,
+                const int *labels, int nlabels, double *part, double *res, hipStream_t s);
+// res: the sums of np.gradient(P, dz, dy, dx)'s three components, in that order
+int launch_gradient_sums(const DragArgs &a, const void *P, double *part, double *res, hipStream_t s);
+
 // ---- linear (ptv_linear.hip): griddata(method='linear') over scipy's Delaunay triangulation ----
 struct LinearKernelArgs {
     int nx, ny;          // grid plane

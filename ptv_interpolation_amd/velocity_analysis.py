@@ -17,8 +17,18 @@ it.
 accumulates in float64 in a fixed order; np.mean sums pairwise (and in float32 for float32 fields),
 so the value agrees with the reference to rounding, not bit for bit.
 
-``compute_pressure_field``, the interface-drag functions and ``compute_permeability_from_pressure``
-stay with the reference.
+``compute_interface_drag`` (:332-511, ``method='staircase'``) and
+``compute_permeability_from_pressure`` (:659-697) consume a pressure field from any source.  The
+drag comes from one pass over the label mask (csrc/ptv_drag.hip behind ``ptv_interface_drag``;
+DESIGN.md §19): the device returns a face count and four float64 sums per (label, axis, direction),
+the host assembles the reference's keys from them in the reference's order.  ``Area`` equals the
+reference bit for bit; the force keys agree to the rounding of a reordered float64 sum (float32
+fields are widened on load, so they are summed more accurately than the reference's float32 sums).
+The result always carries ``Fx``, ``Fy``, ``Fz`` (and ``Mx``, ``My``, ``Mz`` with a ``volume``),
+which the reference's staircase leaves out.  The permeability is the reference's expression of the
+device's float64 sums of u, v, w and of ``np.gradient(pressure)``'s components.
+
+``compute_pressure_field`` and ``compute_interface_drag_mesh`` stay with the reference.
 """
 from __future__ import annotations
 
@@ -27,7 +37,7 @@ import numpy as np
 from . import _lib, launcher
 
 __all__ = ["compute_strain_rate", "compute_viscous_dissipation", "compute_vorticity", "compute_permeability",
-           "compute_astarita_flow_type", "analyze"]
+           "compute_astarita_flow_type", "analyze", "compute_interface_drag", "compute_permeability_from_pressure"]
 
 # np.gradient's message for an axis shorter than edge_order + 1
 _TOO_SMALL = ("Shape of array too small to calculate a numerical gradient, at least (edge_order + 1) elements "
@@ -174,3 +184,141 @@ def analyze(u, v, w, dx, dy, dz, viscosity, mask=None):
                                         st["n_voxels"], viscosity)
     out["stats"] = st
     return out
+
+
+# ---- interface drag (velocity_analysis.py:332-511) ----
+_DRAG_KEYS = ("Fx_v", "Fy_v", "Fz_v", "Fx_v_tan", "Fy_v_tan", "Fz_v_tan", "Fx_v_nor", "Fy_v_nor", "Fz_v_nor",
+              "Fx_p", "Fy_p", "Fz_p", "Area")
+_INT32 = np.iinfo(np.int32)
+
+
+def _scalar_args(dx, dy, dz, viscosity):
+    for h in (dx, dy, dz):
+        if np.ndim(h) != 0:
+            raise NotImplementedError("coordinate-array spacings are not supported on the GPU path (scalars only)")
+        if not (np.isfinite(h) and h > 0):
+            raise ValueError(f"spacings must be positive and finite, got {h!r}")
+    if np.ndim(viscosity) != 0:
+        raise NotImplementedError("viscosity must be a scalar on the GPU path")
+    if not np.isfinite(viscosity):
+        raise ValueError(f"viscosity must be finite, got {viscosity!r}")
+
+
+def _drag_fields(u, v, w, pressure):
+    """u, v, w and the pressure (or None) in one compute dtype, float32 or float64."""
+    fields = [np.asarray(a) for a in (u, v, w)] + ([] if pressure is None else [np.asarray(pressure)])
+    if len({a.shape for a in fields}) != 1 or fields[0].ndim != 3:
+        raise ValueError(f"u, v, w and the pressure must share one 3-D shape, got {[a.shape for a in fields]}")
+    ft = _field_dtype(fields, "fields")
+    if ft.kind in "biu":
+        ft = np.dtype(np.float64)  # numpy computes integer arrays as float64
+    if ft not in (np.float32, np.float64):
+        raise NotImplementedError(f"field dtype {ft} (GPU path: float32 / float64)")
+    return [a.astype(ft, copy=False) for a in fields]
+
+
+def _drag_mask(mask, shape):
+    """The label mask as int32: bool or any integer dtype whose values fit."""
+    mask = np.asarray(mask)
+    if mask.shape != tuple(shape):
+        raise ValueError(f"mask shape {mask.shape} does not match the fields' {tuple(shape)}")
+    if mask.dtype.kind not in "biu":
+        raise NotImplementedError(f"mask dtype {mask.dtype} (GPU path: bool or an integer dtype)")
+    if mask.dtype.kind != "b" and mask.dtype.itemsize >= 4 and mask.dtype != np.int32 and mask.size:
+        if mask.max() > _INT32.max or mask.min() < _INT32.min:
+            raise NotImplementedError("mask values outside the int32 range are not supported on the GPU path")
+    return mask
+
+
+def _assemble_drag(labels, records, dx, dy, dz, volume=None, has_pressure=True):
+    """The reference's result dict from one record per (given label, axis, direction), accumulated
+    in the reference's order: axis 0, 1, 2; the labels as given; direction A, then B.  ``records``
+    is indexable as ``records[i, axis, direction]`` with fields count, sum_p, sum_u, sum_v, sum_w."""
+    results = {}
+    for label in labels:
+        results[label] = dict.fromkeys(_DRAG_KEYS, 0.0)
+    dA = [dy * dx, dz * dx, dz * dy]
+    for axis in range(3):
+        area = dA[axis]
+        normal = "zyx"[axis]
+        for i, label in enumerate(labels):
+            r = results[label]
+            for direction in range(2):
+                rec = records[i, axis, direction]
+                if rec["count"] == 0:  # the reference's np.any(idx)
+                    continue
+                r["Area"] += rec["count"] * area
+                if has_pressure:
+                    r[f"F{normal}_p"] += rec["sum_p"]
+                for comp, s in (("x", rec["sum_u"]), ("y", rec["sum_v"]), ("z", rec["sum_w"])):
+                    r[f"F{comp}_v"] -= s
+                    r[f"F{comp}_v_" + ("nor" if comp == normal else "tan")] -= s
+    for r in results.values():
+        # the mesh method's definitions (:647-655); the reference's staircase leaves them out
+        for c in "xyz":
+            r[f"F{c}"] = r[f"F{c}_v"] + r[f"F{c}_p"]
+        if volume:
+            for c in "xyz":
+                r[f"M{c}"] = r[f"F{c}"] / volume
+    return results
+
+
+def compute_interface_drag(u, v, w, pressure, viscosity, dx, dy, dz, mask, labels=None, method='staircase', mesh_step=1, volume=None, background_mask=None):
+    """velocity_analysis.py:332-511 on the GPU: the staircase drag on every interface between the
+    fluid (mask == 0) and each positive label, a dict of dicts keyed by label.  ``mesh_step`` and
+    ``background_mask`` are unused, as in the reference's staircase.  ``Fx``, ``Fy``, ``Fz`` are
+    always present, ``Mx``, ``My``, ``Mz`` with a truthy ``volume``."""
+    if method == "mesh":
+        raise NotImplementedError("method='mesh' (marching cubes) stays on the host: "
+                                  "the reference's compute_interface_drag_mesh")
+    if method != "staircase":
+        raise ValueError(f"unknown method {method!r} (GPU path: 'staircase')")
+    fields = _drag_fields(u, v, w, pressure)
+    mask = _drag_mask(mask, fields[0].shape)
+    _scalar_args(dx, dy, dz, viscosity)
+    if labels is None:
+        labels = np.unique(mask)
+        labels = labels[labels > 0]
+    if len(labels) == 0:
+        return {}
+    _, slot = _lib.drag_label_table(labels)
+    if mask.size == 0:
+        records = np.zeros((len(slot), 3, 2), dtype=_lib.DRAG_RECORD)
+    else:
+        records, _ = _ctx().interface_drag(mask, fields[0], fields[1], fields[2],
+                                           fields[3] if pressure is not None else None, float(viscosity),
+                                           float(dx), float(dy), float(dz), labels)
+    return _assemble_drag(labels, records, dx, dy, dz, volume, has_pressure=pressure is not None)
+
+
+# ---- permeability from the pressure gradient (velocity_analysis.py:659-697) ----
+def _permeability_from_pressure(sum_u, sum_v, sum_w, sum_gx, sum_gy, sum_gz, n, viscosity):
+    """velocity_analysis.py:673-697 from the sums over the whole volume of u, v, w and of the
+    x, y, z components of the pressure gradient."""
+    n = np.float64(n)
+    U0_vec = np.array([np.float64(s) / n for s in (sum_u, sum_v, sum_w)])
+    grad_P_vec = np.array([np.float64(s) / n for s in (sum_gx, sum_gy, sum_gz)])
+    grad_P_mag2 = np.sum(grad_P_vec**2)
+    if grad_P_mag2 == 0:
+        return 0.0
+    return -viscosity * np.dot(U0_vec, grad_P_vec) / grad_P_mag2
+
+
+def compute_permeability_from_pressure(u, v, w, pressure, viscosity, dx, dy, dz):
+    """velocity_analysis.py:659-697: k = -viscosity * (U0 . G) / |G|^2 with U0 the mean velocity and
+    G the mean of np.gradient(pressure, dz, dy, dx), from the device's float64 sums."""
+    fields, _, (hx, hy, hz), strong = _stencil_args(u, v, w, dx, dy, dz, None)
+    p = np.asarray(pressure)
+    if p.shape != fields[0].shape:
+        raise ValueError(f"pressure shape {p.shape} does not match the fields' {fields[0].shape}")
+    if p.dtype.kind in "biu":
+        p = p.astype(np.float64)
+    if p.dtype != fields[0].dtype:
+        raise NotImplementedError(f"fields of mixed dtypes {sorted(map(str, {p.dtype, fields[0].dtype}))} are not "
+                                  "supported on the GPU path")
+    if np.ndim(viscosity) != 0:
+        raise NotImplementedError("viscosity must be a scalar on the GPU path")
+    ctx = _ctx()
+    _, st = ctx.flow_analysis(*fields, hx, hy, hz, outputs=())
+    gz, gy, gx = ctx.gradient_sums(p, hx, hy, hz, spacing_strong=strong)
+    return _permeability_from_pressure(st["sum_u"], st["sum_v"], st["sum_w"], gx, gy, gz, st["n_voxels"], viscosity)

@@ -1,15 +1,26 @@
 """Repo-root shim for the reference ``velocity_analysis`` module (drop-in, in the manner of the root
 ``physics.py``).
 
-The reference module holds more than the flow analysis: ``compute_pressure_field``, the
-interface-drag functions and ``compute_permeability_from_pressure`` stay on the host.  When the
-reference ``velocity_analysis.py`` is on the path (next to the caller's script), it is loaded under
-a private name and every one of its names is re-exported; ``compute_strain_rate``,
-``compute_viscous_dissipation``, ``compute_vorticity``, ``compute_permeability`` and
-``compute_astarita_flow_type`` (velocity_analysis.py:10-188) are replaced by the MI355X path, here
-and inside the reference module.  The four fields are bit-identical to the reference; the
-permeability agrees to rounding (its means come from float64 device sums).  Without
-the reference module (the GPU box), only the five functions and ``analyze`` are provided.
+The reference module holds more than the flow analysis: ``compute_pressure_field`` and the mesh
+interface drag stay on the host, and by default so do ``compute_interface_drag`` and
+``compute_permeability_from_pressure``.  When the reference ``velocity_analysis.py`` is on the path
+(next to the caller's script), it is loaded under a private name and every one of its names is
+re-exported; ``compute_strain_rate``, ``compute_viscous_dissipation``, ``compute_vorticity``,
+``compute_permeability`` and ``compute_astarita_flow_type`` (velocity_analysis.py:10-188) are
+replaced by the MI355X path, here and inside the reference module.  The four fields are
+bit-identical to the reference; the permeability agrees to rounding (its means come from float64
+device sums).
+
+With ``PTV_GPU_DRAG=1`` in the environment when this module is imported, ``compute_interface_drag``
+(the staircase method, :332-511) and ``compute_permeability_from_pressure`` (:659-697) are replaced
+in the same way.  ``method='mesh'`` is forwarded to the reference's ``compute_interface_drag_mesh``;
+where that function falls back to the staircase (no scikit-image), the fallback lands on the GPU.
+The GPU drag agrees with the reference to the rounding of a reordered sum and adds the keys ``Fx``,
+``Fy``, ``Fz`` (``Mx``, ``My``, ``Mz`` with a volume) that the reference's staircase leaves out
+(INTEGRATION.md).
+
+Without the reference module (the GPU box), the five functions, ``analyze`` and the two GPU
+functions above are provided.
 
 This module is found instead of the reference's when the repository root precedes the reference's
 directory on ``sys.path``.  A script started from inside the reference's directory
@@ -23,6 +34,7 @@ from ptv_interpolation_amd import velocity_analysis as _gpu
 
 _NAMES = ("compute_strain_rate", "compute_viscous_dissipation", "compute_vorticity", "compute_permeability",
           "compute_astarita_flow_type")
+_DRAG_NAMES = ("compute_interface_drag", "compute_permeability_from_pressure")
 _ROOT = _os.path.dirname(_os.path.abspath(__file__))
 
 
@@ -55,3 +67,28 @@ for _n in _NAMES:
     if _ref is not None:
         setattr(_ref, _n, getattr(_gpu, _n))
 analyze = _gpu.analyze
+
+
+def _drag_with_host_mesh(mesh):
+    """The GPU staircase drag with the reference's signature; ``method='mesh'`` goes to the host's
+    ``compute_interface_drag_mesh`` as the reference's own dispatch does (:340-342)."""
+    def compute_interface_drag(u, v, w, pressure, viscosity, dx, dy, dz, mask, labels=None, method='staircase', mesh_step=1, volume=None, background_mask=None):
+        if method == 'mesh':
+            return mesh(u, v, w, pressure, viscosity, dx, dy, dz, mask, labels,
+                        mesh_step=mesh_step, volume=volume, background_mask=background_mask)
+        return _gpu.compute_interface_drag(u, v, w, pressure, viscosity, dx, dy, dz, mask, labels, method, mesh_step,
+                                           volume, background_mask)
+    compute_interface_drag.__doc__ = _gpu.compute_interface_drag.__doc__
+    return compute_interface_drag
+
+
+if _ref is None:
+    for _n in _DRAG_NAMES:
+        globals()[_n] = getattr(_gpu, _n)
+elif _os.environ.get("PTV_GPU_DRAG") == "1":
+    _mesh = getattr(_ref, "compute_interface_drag_mesh", None)
+    _new = {"compute_interface_drag": _drag_with_host_mesh(_mesh) if _mesh else _gpu.compute_interface_drag,
+            "compute_permeability_from_pressure": _gpu.compute_permeability_from_pressure}
+    for _n, _f in _new.items():
+        globals()[_n] = _f
+        setattr(_ref, _n, _f)
