@@ -408,6 +408,49 @@ typedef struct {
     double sum_p, sum_u, sum_v, sum_w;
 } ptv_drag_stats;
 
+/*
+ * Exact Euclidean distance transform of a byte mask and the alignment score that reads it
+ * (auto_align.find_best_offset, auto_align.py:10-62).  The mask is uint8 (nz, ny, nx) C order; the
+ * meaning is scipy.ndimage.distance_transform_edt's with unit spacing: for every nonzero voxel the
+ * distance to the nearest zero voxel, 0 at zero voxels.  d2 is the integer squared distance and the
+ * float64 field is sqrt((double)d2), correctly rounded: both equal scipy's bit for bit.  The
+ * passes work in uint32, so nz^2 + ny^2 + nx^2 must stay below 2^31 (PTV_E_UNSUPPORTED, decided
+ * before any allocation or copy).  A mask without a zero voxel is PTV_E_ARG (scipy measures to a
+ * voxel that is not there).
+ * PTV_API_VERSION is not raised: the presence of ptv_abi_sizes8 is the capability probe.
+ */
+typedef struct {
+    int64_t nx, ny, nz;  /* positive */
+    int keep_distance;   /* nonzero: the float64 field also stays in the context for ptv_align_score */
+} ptv_edt_params;
+
+typedef struct {
+    int64_t max_d2;      /* the maximum of d2 over the volume (an integer reduction) */
+    double ms;           /* the kernels of the call, hipEvent based */
+} ptv_edt_stats;
+
+/*
+ * The alignment objective for a batch of offsets.  points: float64 (n_points, 3) as x, y, z; dt: the
+ * float64 distance field (nz, ny, nx); offsets: float64 (n_offsets, 3) as dx, dy, dz, HOST memory
+ * in both calls.  Per offset o and point p, in the reference's arithmetic: s = p + o in float64,
+ * rint(s) (half to even, as np.round: -0.5 gives index 0), the test against [0, nx) x [0, ny) x
+ * [0, nz) in floating point, and a point inside adds dt[iz, iy, ix].  Coordinates must be finite
+ * (the caller checks).  The reference's value is 1e9 when n_inside == 0, else
+ * sum + n_outside * max(dt); the caller forms it.
+ */
+typedef struct {
+    int64_t nx, ny, nz;  /* positive */
+    int64_t n_points;    /* 0 <= n_points < 2^31 */
+    int n_offsets;       /* >= 1 */
+} ptv_align_params;
+
+/* One record per offset.  sum is float64 in a fixed order (no atomics): the same bits on every
+ * call, and a batch of m offsets gives the bits of m single calls. */
+typedef struct {
+    int64_t n_inside, n_outside;
+    double sum;
+} ptv_align_record;
+
 /* Library / device management. */
 int ptv_version(void);
 /* sizeof(ptv_particles, ptv_grid, ptv_knn_params, ptv_stats, ptv_rbf_params, ptv_div_params):
@@ -428,6 +471,10 @@ int ptv_abi_sizes6(int64_t out2[2]);
 /* sizeof(ptv_drag_params, ptv_drag_stats): the same self-check.  A library that has this symbol has
  * the interface drag and gradient sums entry points (PTV_API_VERSION stays 11). */
 int ptv_abi_sizes7(int64_t out2[2]);
+/* sizeof(ptv_edt_params, ptv_edt_stats, ptv_align_params, ptv_align_record): the same self-check.  A
+ * library that has this symbol has the distance transform and alignment score entry points
+ * (PTV_API_VERSION stays 11). */
+int ptv_abi_sizes8(int64_t out4[4]);
 const char *ptv_last_error(void);
 int ptv_device_count(int *out);
 int ptv_init(int device, ptv_ctx **out);
@@ -662,6 +709,35 @@ int ptv_gradient_sums(ptv_ctx *ctx, const ptv_flow_params *prm, const void *P, d
 
 /* Same on a device pointer, enqueued on `stream` (NULL = the ctx's own); synchronises. */
 int ptv_gradient_sums_dev(ptv_ctx *ctx, const ptv_flow_params *prm, const void *P, void *stream, double sums3[3]);
+
+/*
+ * Distance transform, host buffers: H2D of the mask, the x pass and two envelope passes, D2H of what
+ * was asked for.  d2 (int32, nx * ny * nz) and dist (float64, the same count) may each be NULL.
+ * With prm->keep_distance the float64 field is computed in any case and stays in the context, where
+ * a later ptv_align_score with dt == NULL reads it.  st may be NULL.
+ */
+int ptv_edt(ptv_ctx *ctx, const ptv_edt_params *prm, const uint8_t *mask, int32_t *d2, double *dist,
+            ptv_edt_stats *st);
+
+/* Same on device pointers, enqueued on `stream` (NULL = the ctx's own); synchronises (the maximum
+ * is returned, and decides the no-zero error). */
+int ptv_edt_dev(ptv_ctx *ctx, const ptv_edt_params *prm, const uint8_t *mask, int32_t *d2, double *dist,
+                void *stream, ptv_edt_stats *st);
+
+/*
+ * Alignment score, host buffers.  points and dt are uploaded into the context and stay there: a
+ * later call may pass NULL for either to score against what the context holds (the dimensions and
+ * the point count must be those of the upload, PTV_E_ARG otherwise), so that an optimiser's calls
+ * move only the offsets and the records.  dt == NULL also reads the field a ptv_edt with
+ * keep_distance left.  records: n_offsets entries.  ms (may be NULL): the kernels' time.
+ */
+int ptv_align_score(ptv_ctx *ctx, const ptv_align_params *prm, const double *points, const double *dt,
+                    const double *offsets, ptv_align_record *records, double *ms);
+
+/* Same on device pointers (points, dt; offsets and records stay host memory), enqueued on `stream`
+ * (NULL = the ctx's own); synchronises (the records are returned). */
+int ptv_align_score_dev(ptv_ctx *ctx, const ptv_align_params *prm, const double *points, const double *dt,
+                        const double *offsets, void *stream, ptv_align_record *records, double *ms);
 
 /*
  * Last-launch k-NN kernel duration in ms (hipEvent pair recorded around the

@@ -179,6 +179,27 @@ class DragStats(C.Structure):
 DRAG_RECORD = np.dtype([("count", np.int64), ("sum_p", np.float64), ("sum_u", np.float64), ("sum_v", np.float64),
                         ("sum_w", np.float64)])
 
+class EdtParams(C.Structure):
+    _fields_ = [("nx", C.c_int64), ("ny", C.c_int64), ("nz", C.c_int64), ("keep_distance", C.c_int)]
+
+
+class EdtStats(C.Structure):
+    _fields_ = [("max_d2", C.c_int64), ("ms", C.c_double)]
+
+
+class AlignParams(C.Structure):
+    _fields_ = [("nx", C.c_int64), ("ny", C.c_int64), ("nz", C.c_int64), ("n_points", C.c_int64),
+                ("n_offsets", C.c_int)]
+
+
+class AlignRecord(C.Structure):
+    """One offset's record of the alignment score."""
+    _fields_ = [("n_inside", C.c_int64), ("n_outside", C.c_int64), ("sum", C.c_double)]
+
+
+# the records as a numpy array: (n_offsets,) of this dtype
+ALIGN_RECORD = np.dtype([("n_inside", np.int64), ("n_outside", np.int64), ("sum", np.float64)])
+
 MASK_BOOL = 0
 MASK_BITS = 1
 
@@ -276,6 +297,11 @@ EXPORTS = {
     "ptv_interface_drag_dev": (C.c_int, [C.c_void_p, C.POINTER(DragParams)] + [C.c_void_p] * 7 + [_dp]),
     "ptv_gradient_sums": (C.c_int, [C.c_void_p, C.POINTER(FlowParams), C.c_void_p, _dp]),
     "ptv_gradient_sums_dev": (C.c_int, [C.c_void_p, C.POINTER(FlowParams), C.c_void_p, C.c_void_p, _dp]),
+    "ptv_abi_sizes8": (C.c_int, [C.POINTER(C.c_int64)]),
+    "ptv_edt": (C.c_int, [C.c_void_p, C.POINTER(EdtParams)] + [C.c_void_p] * 3 + [C.POINTER(EdtStats)]),
+    "ptv_edt_dev": (C.c_int, [C.c_void_p, C.POINTER(EdtParams)] + [C.c_void_p] * 4 + [C.POINTER(EdtStats)]),
+    "ptv_align_score": (C.c_int, [C.c_void_p, C.POINTER(AlignParams)] + [C.c_void_p] * 4 + [_dp]),
+    "ptv_align_score_dev": (C.c_int, [C.c_void_p, C.POINTER(AlignParams)] + [C.c_void_p] * 5 + [_dp]),
     "ptv_last_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     "ptv_debug_stamps": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double)]),
 }
@@ -392,6 +418,24 @@ def abi_sizes7():
     out = (C.c_int64 * 2)()
     check(lib().ptv_abi_sizes7(out))
     return list(out), [C.sizeof(DragParams), C.sizeof(DragStats)]
+
+
+def abi_sizes8():
+    """(C sizeof, ctypes sizeof) of ptv_edt_params, ptv_edt_stats, ptv_align_params, ptv_align_record."""
+    out = (C.c_int64 * 4)()
+    check(lib().ptv_abi_sizes8(out))
+    return list(out), [C.sizeof(EdtParams), C.sizeof(EdtStats), C.sizeof(AlignParams), C.sizeof(AlignRecord)]
+
+
+def edt_check_shape(shape):
+    """The (nz, ny, nx) a 32-bit squared distance can hold: 3-D and nz^2 + ny^2 + nx^2 < 2^31
+    (``NotImplementedError`` otherwise).  Looks at the shape alone."""
+    if len(shape) != 3:
+        raise NotImplementedError(f"the GPU distance transform is 3-D only (got {len(shape)}-D)")
+    if sum(int(n) * int(n) for n in shape) >= 2**31:
+        raise NotImplementedError(f"shape {tuple(shape)}: nz^2 + ny^2 + nx^2 must be below 2^31 "
+                                  "(squared distances are 32-bit on the GPU)")
+    return tuple(int(n) for n in shape)
 
 
 def drag_label_table(labels):
@@ -1113,3 +1157,90 @@ class Context:
         out = (C.c_double * 3)()
         check(lib().ptv_gradient_sums_dev(self.h, C.byref(prm), C.c_void_p(ptr), C.c_void_p(stream or 0), out))
         return [float(x) for x in out]
+
+    # -- distance transform and alignment score (auto_align.py:10-62) ----
+    def edt(self, mask, want_d2=True, want_distance=True, keep_distance=False):
+        """Exact Euclidean distance transform of a host uint8 (nz, ny, nx) ``mask`` (scipy's meaning:
+        per nonzero voxel the distance to the nearest zero voxel).  Returns ``(d2, dist, stats)``:
+        the int32 squared distances and the float64 distances (None where not asked for) and
+        ``{"max_d2", "ms"}``.  ``keep_distance`` leaves the float64 field in the context for
+        ``align_score(..., dt=None)``.  ``ValueError`` when the mask has no zero voxel."""
+        nz, ny, nx = edt_check_shape(mask.shape)
+        mk = np.ascontiguousarray(mask, dtype=np.uint8)
+        d2 = np.empty(mk.shape, dtype=np.int32) if want_d2 else None
+        dist = np.empty(mk.shape, dtype=np.float64) if want_distance else None
+        prm = EdtParams(nx, ny, nz, int(bool(keep_distance)))
+        st = EdtStats()
+        self._align_owner = None  # the resident field is rewritten: no session's upload survives
+        check(lib().ptv_edt(self.h, C.byref(prm), mk.ctypes.data_as(C.c_void_p),
+                            d2.ctypes.data_as(C.c_void_p) if want_d2 else None,
+                            dist.ctypes.data_as(C.c_void_p) if want_distance else None, C.byref(st)))
+        return d2, dist, {"max_d2": int(st.max_d2), "ms": st.ms}
+
+    def edt_dev(self, nx, ny, nz, mask_ptr, d2_ptr=0, dist_ptr=0, keep_distance=False, stream=0):
+        """The same for a uint8 mask resident in HBM; ``d2_ptr`` (int32) and ``dist_ptr`` (float64)
+        are device pointers, 0 = not wanted.  Returns the stats."""
+        edt_check_shape((nz, ny, nx))
+        prm = EdtParams(nx, ny, nz, int(bool(keep_distance)))
+        st = EdtStats()
+        check(lib().ptv_edt_dev(self.h, C.byref(prm), C.c_void_p(mask_ptr), C.c_void_p(d2_ptr) if d2_ptr else None,
+                                C.c_void_p(dist_ptr) if dist_ptr else None, C.c_void_p(stream or 0), C.byref(st)))
+        return {"max_d2": int(st.max_d2), "ms": st.ms}
+
+    def _align_call(self, fn, shape, n_points, ptrs, offsets, extra=()):
+        nz, ny, nx = shape
+        off = np.ascontiguousarray(offsets, dtype=np.float64).reshape(-1, 3)
+        rec = np.zeros(off.shape[0], dtype=ALIGN_RECORD)
+        if off.shape[0] == 0:
+            return rec, 0.0
+        prm = AlignParams(nx, ny, nz, int(n_points), int(off.shape[0]))
+        ms = C.c_double(0.0)
+        check(fn(self.h, C.byref(prm), *[C.c_void_p(p) if p else None for p in ptrs], off.ctypes.data_as(C.c_void_p),
+                 *extra, rec.ctypes.data_as(C.c_void_p), C.byref(ms)))
+        return rec, ms.value
+
+    def align_score(self, shape, n_points, offsets, points=None, dt=None):
+        """The alignment records of ``offsets`` (m, 3).  ``points`` (n, 3) float64 and ``dt`` (nz, ny, nx)
+        float64 are uploaded and stay in the context; None scores against what it holds (``shape`` and
+        ``n_points`` must be the upload's).  Returns ``(records, ms)``, records of ALIGN_RECORD."""
+        keep = []
+        for a in (points, dt):
+            keep.append(None if a is None else np.ascontiguousarray(a, dtype=np.float64))
+        if keep[0] is not None and keep[0].shape != (int(n_points), 3):
+            raise ValueError(f"points must be ({n_points}, 3), got {keep[0].shape}")
+        if keep[1] is not None and keep[1].shape != tuple(shape):
+            raise ValueError(f"dt must be {tuple(shape)}, got {keep[1].shape}")
+        return self._align_call(lib().ptv_align_score, shape, n_points,
+                                [0 if a is None else a.ctypes.data for a in keep], offsets)
+
+    def align_score_dev(self, shape, n_points, points_ptr, dt_ptr, offsets, stream=0):
+        """The same for points and a distance field resident in HBM (device pointers)."""
+        return self._align_call(lib().ptv_align_score_dev, shape, n_points, [points_ptr, dt_ptr], offsets,
+                                extra=(C.c_void_p(stream or 0),))
+
+
+class AlignSession:
+    """Points and a distance field uploaded once, offsets scored against them: what an optimiser
+    that evaluates the objective some tens of times needs.  ``dt`` None takes the field the
+    context's last ``edt(..., keep_distance=True)`` left.  The resident buffers belong to the
+    context; a session that finds another one has used them since uploads again."""
+
+    def __init__(self, ctx, points, shape, dt=None):
+        self.ctx = ctx
+        self.shape = tuple(int(n) for n in shape)
+        self.points = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        self.dt = dt
+        self.ms = 0.0
+        self.calls = 0
+
+    def score(self, offsets):
+        """Records (ALIGN_RECORD) of the offsets (m, 3)."""
+        mine = getattr(self.ctx, "_align_owner", None) is self
+        if not mine and self.dt is None and getattr(self.ctx, "_align_owner", None) is not None:
+            raise RuntimeError("AlignSession: the context's kept distance field has been replaced by another session")
+        rec, ms = self.ctx.align_score(self.shape, len(self.points), offsets,
+                                       points=None if mine else self.points, dt=None if mine else self.dt)
+        self.ctx._align_owner = self
+        self.ms += ms
+        self.calls += 1
+        return rec

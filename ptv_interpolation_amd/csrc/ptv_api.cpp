@@ -106,6 +106,18 @@ int ptv_abi_sizes7(int64_t out2[2]) {
     return PTV_OK;
 }
 
+int ptv_abi_sizes8(int64_t out4[4]) {
+    if (!out4) {
+        set_error("ptv_abi_sizes8: out is NULL");
+        return PTV_E_ARG;
+    }
+    out4[0] = (int64_t)sizeof(ptv_edt_params);
+    out4[1] = (int64_t)sizeof(ptv_edt_stats);
+    out4[2] = (int64_t)sizeof(ptv_align_params);
+    out4[3] = (int64_t)sizeof(ptv_align_record);
+    return PTV_OK;
+}
+
 const char *ptv_last_error(void) { return g_last_error.c_str(); }
 
 int ptv_device_count(int *out) {
@@ -1319,6 +1331,177 @@ int ptv_gradient_sums(ptv_ctx *c, const ptv_flow_params *prm, const void *P, dou
     PTV_TRY(c->drag_fld[3].ensure(bytes));
     PTV_HIP(hipMemcpyAsync(c->drag_fld[3].p, P, bytes, hipMemcpyHostToDevice, c->stream));
     return ptv_gradient_sums_dev(c, prm, c->drag_fld[3].p, c->stream, sums3);
+}
+
+// ---- distance transform and alignment score (ptv_edt.hip) ----
+// the dimensions a uint32 squared distance can hold; decided before any allocation or copy
+static int edt_dims(int64_t nx, int64_t ny, int64_t nz, const char *what) {
+    if (nx < 1 || ny < 1 || nz < 1) {
+        set_error(std::string(what) + ": dimensions must be positive");
+        return PTV_E_ARG;
+    }
+    const int64_t most = 46340;  // floor(sqrt(2^31 - 1)): keeps the squares below from overflowing
+    if (nx > most || ny > most || nz > most || nx * nx + ny * ny + nz * nz >= ((int64_t)1 << 31)) {
+        set_error(std::string(what) + ": nz^2 + ny^2 + nx^2 must be below 2^31 (squared distances are 32-bit)");
+        return PTV_E_UNSUPPORTED;
+    }
+    return PTV_OK;
+}
+
+int ptv_edt_dev(ptv_ctx *c, const ptv_edt_params *prm, const uint8_t *mask, int32_t *d2, double *dist, void *stream,
+                ptv_edt_stats *st) {
+    if (!c || !prm || !mask) {
+        set_error("distance transform: NULL context, params or mask");
+        return PTV_E_ARG;
+    }
+    PTV_TRY(edt_dims(prm->nx, prm->ny, prm->nz, "distance transform"));
+    PTV_HIP(hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    const size_t n = (size_t)(prm->nx * prm->ny * prm->nz);
+    PTV_TRY(c->edt_a.ensure(n));
+    PTV_TRY(c->edt_b.ensure(n));
+    PTV_TRY(c->edt_max.ensure(1));
+    double *kept = nullptr;
+    if (prm->keep_distance) {
+        c->align_dt_dims[0] = 0;  // nothing valid until this call has succeeded
+        PTV_TRY(c->align_dt.ensure(n));
+        kept = c->align_dt.p;
+    }
+    PTV_TRY(c->ev_edt0.record(s));
+    // with both a caller's field and a kept one, the kernel writes the kept one and a copy follows
+    PTV_TRY(launch_edt((int)prm->nx, (int)prm->ny, (int)prm->nz, mask, c->edt_a.p, c->edt_b.p, d2, kept ? kept : dist,
+                       c->edt_max.p, s));
+    if (kept && dist) PTV_HIP(hipMemcpyAsync(dist, kept, n * sizeof(double), hipMemcpyDeviceToDevice, s));
+    PTV_TRY(c->ev_edt1.record(s));
+    unsigned top = 0;
+    PTV_HIP(hipMemcpyAsync(&top, c->edt_max.p, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    PTV_HIP(hipStreamSynchronize(s));
+    if (top >= 0x80000000u) {
+        set_error("distance transform: the mask has no zero voxel");
+        return PTV_E_ARG;
+    }
+    if (kept) {
+        c->align_dt_dims[0] = prm->nx;
+        c->align_dt_dims[1] = prm->ny;
+        c->align_dt_dims[2] = prm->nz;
+    }
+    if (st) {
+        float t = 0.f;
+        PTV_HIP(hipEventElapsedTime(&t, c->ev_edt0, c->ev_edt1));
+        st->max_d2 = (int64_t)top;
+        st->ms = t;
+    }
+    return PTV_OK;
+}
+
+int ptv_edt(ptv_ctx *c, const ptv_edt_params *prm, const uint8_t *mask, int32_t *d2, double *dist, ptv_edt_stats *st) {
+    if (!c || !prm || !mask) {
+        set_error("distance transform: NULL context, params or mask");
+        return PTV_E_ARG;
+    }
+    PTV_TRY(edt_dims(prm->nx, prm->ny, prm->nz, "distance transform"));
+    PTV_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const size_t n = (size_t)(prm->nx * prm->ny * prm->nz);
+    PTV_TRY(c->edt_mask.ensure(n));
+    if (d2) PTV_TRY(c->edt_d2.ensure(n));
+    // the float64 field of a host call lives in the context's resident buffer, kept or not
+    ptv_edt_params q = *prm;
+    const bool kept = prm->keep_distance != 0;
+    if (dist) q.keep_distance = 1;
+    PTV_HIP(hipMemcpyAsync(c->edt_mask.p, mask, n, hipMemcpyHostToDevice, s));
+    const int rc = ptv_edt_dev(c, &q, c->edt_mask.p, d2 ? c->edt_d2.p : nullptr, nullptr, s, st);
+    if (!kept) c->align_dt_dims[0] = 0;
+    PTV_TRY(rc);
+    if (d2) PTV_HIP(hipMemcpyAsync(d2, c->edt_d2.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (dist) PTV_HIP(hipMemcpyAsync(dist, c->align_dt.p, n * sizeof(double), hipMemcpyDeviceToHost, s));
+    PTV_HIP(hipStreamSynchronize(s));
+    return PTV_OK;
+}
+
+static int align_check(ptv_ctx *c, const ptv_align_params *prm, const double *offsets, ptv_align_record *records) {
+    if (!c || !prm || !offsets || !records) {
+        set_error("alignment score: NULL context, params, offsets or records");
+        return PTV_E_ARG;
+    }
+    PTV_TRY(edt_dims(prm->nx, prm->ny, prm->nz, "alignment score"));
+    if (prm->n_points < 0 || prm->n_points >= ((int64_t)1 << 31)) {
+        set_error("alignment score: 0 <= n_points < 2^31");
+        return PTV_E_ARG;
+    }
+    if (prm->n_offsets < 1) {
+        set_error("alignment score: at least one offset");
+        return PTV_E_ARG;
+    }
+    return PTV_OK;
+}
+
+int ptv_align_score_dev(ptv_ctx *c, const ptv_align_params *prm, const double *points, const double *dt,
+                        const double *offsets, void *stream, ptv_align_record *records, double *ms) {
+    PTV_TRY(align_check(c, prm, offsets, records));
+    if (!dt || (!points && prm->n_points > 0)) {
+        set_error("alignment score: NULL points or distance field");
+        return PTV_E_ARG;
+    }
+    PTV_HIP(hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    AlignArgs a{};
+    a.nx = (int)prm->nx;
+    a.ny = (int)prm->ny;
+    a.nz = (int)prm->nz;
+    a.n = prm->n_points;
+    align_tile(a);
+    const int chunk = 4096;  // offsets per launch (a grid's y extent is 16-bit)
+    const int m = prm->n_offsets, mc = std::min(m, chunk);
+    PTV_TRY(c->align_off.ensure((size_t)m * 3));
+    PTV_TRY(c->align_rec.ensure((size_t)m));
+    PTV_TRY(c->align_psum.ensure((size_t)mc * a.nblocks));
+    PTV_TRY(c->align_pcnt.ensure((size_t)mc * a.nblocks));
+    PTV_HIP(hipMemcpyAsync(c->align_off.p, offsets, (size_t)m * 3 * sizeof(double), hipMemcpyHostToDevice, s));
+    PTV_TRY(c->ev_edt0.record(s));
+    for (int o0 = 0; o0 < m; o0 += chunk)
+        PTV_TRY(launch_align_score(a, points, dt, c->align_off.p + (size_t)o0 * 3, std::min(chunk, m - o0),
+                                   c->align_psum.p, c->align_pcnt.p, c->align_rec.p + o0, s));
+    PTV_TRY(c->ev_edt1.record(s));
+    PTV_HIP(hipMemcpyAsync(records, c->align_rec.p, (size_t)m * sizeof(ptv_align_record), hipMemcpyDeviceToHost, s));
+    PTV_HIP(hipStreamSynchronize(s));
+    if (ms) {
+        float t = 0.f;
+        PTV_HIP(hipEventElapsedTime(&t, c->ev_edt0, c->ev_edt1));
+        *ms = t;
+    }
+    return PTV_OK;
+}
+
+int ptv_align_score(ptv_ctx *c, const ptv_align_params *prm, const double *points, const double *dt,
+                    const double *offsets, ptv_align_record *records, double *ms) {
+    PTV_TRY(align_check(c, prm, offsets, records));
+    PTV_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    if (dt) {
+        const size_t n = (size_t)(prm->nx * prm->ny * prm->nz);
+        c->align_dt_dims[0] = 0;
+        PTV_TRY(c->align_dt.ensure(n));
+        PTV_HIP(hipMemcpyAsync(c->align_dt.p, dt, n * sizeof(double), hipMemcpyHostToDevice, s));
+        c->align_dt_dims[0] = prm->nx;
+        c->align_dt_dims[1] = prm->ny;
+        c->align_dt_dims[2] = prm->nz;
+    } else if (c->align_dt_dims[0] != prm->nx || c->align_dt_dims[1] != prm->ny || c->align_dt_dims[2] != prm->nz) {
+        set_error("alignment score: dt is NULL and the context holds no distance field of these dimensions");
+        return PTV_E_ARG;
+    }
+    if (points) {
+        c->align_pts_n = -1;
+        PTV_TRY(c->align_pts.ensure((size_t)prm->n_points * 3));
+        PTV_HIP(hipMemcpyAsync(c->align_pts.p, points, (size_t)prm->n_points * 3 * sizeof(double),
+                               hipMemcpyHostToDevice, s));
+        c->align_pts_n = prm->n_points;
+    } else if (c->align_pts_n != prm->n_points) {
+        set_error("alignment score: points is NULL and the context holds no point set of this size");
+        return PTV_E_ARG;
+    }
+    PTV_TRY(c->align_pts.ensure(1));  // zero points: still a pointer
+    return ptv_align_score_dev(c, prm, c->align_pts.p, c->align_dt.p, offsets, s, records, ms);
 }
 
 int ptv_last_stats(ptv_ctx *c, ptv_stats *st) {

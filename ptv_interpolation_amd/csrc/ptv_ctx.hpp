@@ -104,6 +104,16 @@ struct ptv_ctx {
     ptv::DevBuf<int> drag_labels, drag_mask;                          // the label table; the mask of the host calls
     ptv::DevBuf<uint8_t> drag_fld[4];                                 // the host calls' U, V, W, P
     ptv::Event ev_drag0, ev_drag1;                                    // around its kernels
+    ptv::DevBuf<unsigned> edt_a, edt_b, edt_max;                      // distance transform: pass buffers, max(d2)
+    ptv::DevBuf<uint8_t> edt_mask;                                    // its host calls: the mask
+    ptv::DevBuf<int> edt_d2;                                          //   and d2
+    ptv::DevBuf<double> align_dt, align_pts;                          // alignment score: resident field and points
+    int64_t align_dt_dims[3] = {0, 0, 0};                             //   what they hold (nx, ny, nz; 0: nothing)
+    int64_t align_pts_n = -1;                                         //   (-1: nothing)
+    ptv::DevBuf<double> align_off, align_psum;                        // offsets, per-block partial sums
+    ptv::DevBuf<int> align_pcnt;                                      //   and inside counts
+    ptv::DevBuf<ptv_align_record> align_rec;                          // one record per offset
+    ptv::Event ev_edt0, ev_edt1;                                      // around the kernels of either
     ptv::PinnedBuf<double> h_bbox;                                    // pinned, kHostWords doubles
     ptv::PinnedBuf<unsigned long long> h_misc;  // pinned scratch words (cull count, halo bound, repair count)
     ptv_stats last{};

@@ -1,6 +1,7 @@
 // ptv_kernels.hpp — host-side launchers for the device kernels.
 #pragma once
 
+#include "../../include/ptv_api.h"
 #include "ptv_common.hpp"
 
 namespace ptv {
@@ -252,6 +253,35 @@ int launch_drag(const DragArgs &a, const int *M, const void *U, const void *V, c
                 const int *labels, int nlabels, double *part, double *res, hipStream_t s);
 // res: the sums of np.gradient(P, dz, dy, dx)'s three components, in that order
 int launch_gradient_sums(const DragArgs &a, const void *P, double *part, double *res, hipStream_t s);
+
+// ---- distance transform and alignment score (ptv_edt.hip) ----
+// An envelope pass stages its 64-column tile in LDS up to this axis length (n * 64 * 4 B = 160 KB,
+// the whole LDS of a compute unit, at 640); longer axes read the previous pass's buffer.
+constexpr int kEdtStagedMax = 640;
+// the columns of one envelope pass: element k of column c is at (c / inner) * outer + c % inner + k * stride
+struct EdtCols {
+    int64_t ncols;
+    int n;
+    int64_t stride, inner, outer;
+};
+// M: the uint8 mask (nz, ny, nx); A, B: nx * ny * nz uint32 of workspace each; d2 (int32) and dist
+// (float64) may each be NULL; *vmax receives max(d2), 2^31 when the mask has no zero voxel.  The
+// caller has checked nz^2 + ny^2 + nx^2 < 2^31.
+int launch_edt(int nx, int ny, int nz, const uint8_t *M, unsigned *A, unsigned *B, int *d2, double *dist,
+               unsigned *vmax, hipStream_t s);
+
+constexpr int kAlignMinItems = 16;     // points per lane of the smallest block
+constexpr int kAlignMaxBlocks = 1024;  // per offset: beyond it the blocks grow, so at most this many partials
+struct AlignArgs {
+    int nx, ny, nz;         // the distance field: (nz, ny, nx) C order
+    int64_t n;              // points, (n, 3) float64 as x, y, z
+    int64_t span = 0;       // points per block (set by align_tile)
+    unsigned nblocks = 0;   // blocks = partials per offset (set by align_tile)
+};
+void align_tile(AlignArgs &a);
+// off: m offsets (m, 3) on the device, m <= 65535; psum, pcnt: m * a.nblocks partials; rec: m records
+int launch_align_score(const AlignArgs &a, const double *P, const double *DT, const double *off, int m, double *psum,
+                       int *pcnt, ptv_align_record *rec, hipStream_t s);
 
 // ---- linear (ptv_linear.hip): griddata(method='linear') over scipy's Delaunay triangulation ----
 struct LinearKernelArgs {
