@@ -396,7 +396,9 @@ int launch_knn(const KnnLaunch &a, const Binned &b, const double *ax, const doub
     ka.gate_halo = a.gate_halo;
     // union seeds (k > 8): the first ~3/4 of each corner's list; the 8 corners' union still holds
     // k distinct particles (else the lattice bound): 512^3 / 5M same-box, IDW k = 50 115.4 ->
-    // 114.1 ms at 36 of 50, Sibson k = 30 58.4 -> 57.5 ms at 22 of 30
+    // 114.1 ms at 36 of 50, Sibson k = 30 58.4 -> 57.5 ms at 22 of 30.  k <= 8 keeps every record:
+    // the looser bound costs more than the shorter seed loop saves (k = 8 main launch 13.7 ms at 8
+    // of 8, 14.0 at 6, 15.1 at 4; profiles/r09_seeds/ab.txt)
     ka.seed_n = a.k > 8 ? (3 * a.k + 3) / 4 : a.k;
     if (const char *e = dev_knob("PTV_SEED_N")) ka.seed_n = std::max(1, std::min(a.k, std::atoi(e)));  // dev knob
     if (a.mode == kModeSlots && (a.slots == nullptr || (a.z0 - ka.lz0) % 4 != 0)) {

@@ -87,6 +87,12 @@ namespace ptv {
 #ifndef PTV_K1_BROADCAST_SEEDS
 #define PTV_K1_BROADCAST_SEEDS 1  // one-slot list: corner seeds by lane broadcast (no LDS hash)
 #endif
+// k <= 8 seed network: the seed list padded with far seeds, its first KMAX distances stored and
+// sorted by a min/max network (same-box A/B, 512^3 / 5M, profiles/r09_seeds/ab.txt: headline main
+// launch 13.56-13.62 -> 13.37-13.45 ms, 3260 -> 3209 VALU per wave)
+#ifndef PTV_SEED_PEEL
+#define PTV_SEED_PEEL 1
+#endif
 #ifndef PTV_SEED_UNROLL_FILTER
 #define PTV_SEED_UNROLL_FILTER 1
 #endif
@@ -1113,20 +1119,64 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(knn_waves<K
                 }
                 // seed-voxel distances are <= Ms; fp32 coordinate + distance error <= Ms * 2^-19
                 const double Ms = uniform(wave_max(pm)) + bhalf;
-                wave_lds_sync();
-                float sd[KMAX];
-#pragma unroll
-                for (int q = 0; q < KMAX; ++q) sd[q] = INFINITY;
-                PTV_UNROLL(PTV_SEED_UNROLL)
-                for (int i = 0; i < nu; i += 2) {
+                // the seeds' fp32 d2 to this lane's voxel, two at a time
+                auto seed_d2 = [&](int i) -> f32x2 {
                     const float2 X = *reinterpret_cast<const float2 *>(fbx + i);
                     const float2 Y = *reinterpret_cast<const float2 *>(fby + i);
                     const float2 Z = *reinterpret_cast<const float2 *>(fbz + i);
                     const f32x2 ex = qf2x - f32x2{X.x, X.y}, ey = qf2y - f32x2{Y.x, Y.y}, ez = qf2z - f32x2{Z.x, Z.y};
                     f32x2 s2 = ex * ex;
                     s2 = __builtin_elementwise_fma(ey, ey, s2);
-                    s2 = __builtin_elementwise_fma(ez, ez, s2);
-                    const float xs[2] = {s2.x, i + 1 < nu ? s2.y : INFINITY};
+                    return __builtin_elementwise_fma(ez, ez, s2);
+                };
+                float sd[KMAX];
+                // PEEL: KMAX + 1 far seeds (d2 = +inf for every voxel) behind the list, so that the
+                // first KMAX are read without a count (fewer than KMAX seeds leave +inf in the
+                // list, as before) and the loop's odd tail needs no select; the first KMAX
+                // distances are stored and ordered by a min/max network (19 exchanges for 8)
+                // instead of KMAX insertion sweeps (KMAX ops each).  The same multiset of
+                // distances goes into the list either way: the k-th is the same float.
+                constexpr bool PEEL = PTV_SEED_PEEL && (KMAX == 2 || KMAX == 4 || KMAX == 8);
+                if constexpr (PEEL) {
+                    if (lane <= KMAX) {  // nu + KMAX <= 72 < kCap
+                        fbx[nu + lane] = INFINITY;
+                        fby[nu + lane] = 0.0f;
+                        fbz[nu + lane] = 0.0f;
+                    }
+                }
+                wave_lds_sync();
+                if constexpr (PEEL) {
+#pragma unroll
+                    for (int q = 0; q < KMAX; q += 2) {
+                        const f32x2 s2 = seed_d2(q);
+                        sd[q] = s2.x;
+                        sd[q + 1] = s2.y;
+                    }
+                    auto cx2 = [&](int i, int j) __attribute__((always_inline)) {
+                        const float lo = __builtin_fminf(sd[i], sd[j]), hi = __builtin_fmaxf(sd[i], sd[j]);
+                        sd[i] = lo;
+                        sd[j] = hi;
+                    };
+                    if constexpr (KMAX == 8) {
+                        cx2(0, 2); cx2(1, 3); cx2(4, 6); cx2(5, 7);
+                        cx2(0, 4); cx2(1, 5); cx2(2, 6); cx2(3, 7);
+                        cx2(0, 1); cx2(2, 3); cx2(4, 5); cx2(6, 7);
+                        cx2(2, 4); cx2(3, 5);
+                        cx2(1, 4); cx2(3, 6);
+                        cx2(1, 2); cx2(3, 4); cx2(5, 6);
+                    } else if constexpr (KMAX == 4) {
+                        cx2(0, 1); cx2(2, 3); cx2(0, 2); cx2(1, 3); cx2(1, 2);
+                    } else {
+                        cx2(0, 1);
+                    }
+                } else {
+#pragma unroll
+                    for (int q = 0; q < KMAX; ++q) sd[q] = INFINITY;
+                }
+                PTV_UNROLL(PTV_SEED_UNROLL)
+                for (int i = PEEL ? KMAX : 0; i < nu; i += 2) {
+                    const f32x2 s2 = seed_d2(i);
+                    const float xs[2] = {s2.x, PEEL || i + 1 < nu ? s2.y : INFINITY};
 #pragma unroll
                     for (int u = 0; u < 2; ++u) {
 #pragma unroll
