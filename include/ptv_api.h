@@ -451,6 +451,52 @@ typedef struct {
     double sum;
 } ptv_align_record;
 
+/*
+ * Pressure recovery (velocity_analysis.compute_pressure_field, velocity_analysis.py:190-330, with
+ * physics.compute_force_divergence and physics.solve_poisson, physics.py:211-345).  All grids are
+ * float64 (nz, ny, nx) C order; the uint8 fluid mask (nonzero = fluid) is required.
+ *   force field   f = mu * laplacian_mask_aware(vel) - rho * (vel . grad) vel, at every voxel,
+ *                 bit-identical to the reference (the fill's np.roll wrap-around included);
+ *   divergence    the face-flux divergence of f at every voxel, bit-identical;
+ *   Poisson       with a Dirichlet grid: scipy's cg(A, b, rtol, atol=0, maxiter) on the masked 7-point
+ *                 Laplacian whose Dirichlet rows and columns are eliminated (values 0: what the
+ *                 reference's matrix computes, bit for bit, from x0 = 0); without one: lsqr on the
+ *                 Neumann system with b - mean(b), the solver of ptv_clean_divergence.
+ * Both solves agree with the host's normwise, not bit for bit (sums in another order).
+ * PTV_API_VERSION is not raised: the presence of ptv_abi_sizes9 is the capability probe.
+ */
+#define PTV_WALL_ZERO_NEUMANN 0
+#define PTV_WALL_INHOMOGENEOUS 1
+#define PTV_ANCHOR_NONE 0
+#define PTV_ANCHOR_OUTLET 1
+#define PTV_ANCHOR_INLET 2
+typedef struct {
+    int64_t nx, ny, nz;
+    double dx, dy, dz;          /* positive and finite */
+    double mu, rho;             /* finite; the advection term is computed for rho > 0 (every extent >= 2) */
+    int wall_bc;                /* PTV_WALL_* */
+    int anchor;                 /* ptv_pressure_recover: PTV_ANCHOR_* */
+    int flow_direction;         /* ptv_pressure_recover: 0 auto (the sign of sum w over fluid), 1 positive, -1 negative */
+    int maxiter;                /* CG, >= 0 */
+    double rtol;                /* CG: stop when ||r|| < rtol * ||b|| at the top of an iteration */
+    double lsqr_damp, lsqr_atol, lsqr_btol; /* the solve without a Dirichlet grid */
+    int lsqr_iter_lim;
+    const uint8_t *fluid_mask;
+} ptv_pressure_params;
+
+typedef struct {
+    int64_t n_fluid, n_dirichlet;
+    int32_t itn;          /* iterations completed */
+    int32_t info;         /* CG: scipy's info (0, or maxiter); LSQR: istop */
+    int32_t solver;       /* 0 CG, 1 LSQR */
+    int32_t anchor_plane; /* ptv_pressure_recover: the z index of the Dirichlet plane, -1 without one */
+    double bnorm, rnorm;  /* ||b||; ||r|| as last summed (LSQR: r2norm) */
+    double sum_abs_fx, sum_abs_fy, sum_abs_fz, sum_w; /* over the fluid voxels (fixed order, no atomics) */
+    double ms_force, ms_divergence, ms_solve; /* hipEvent based; 0 for a stage the call did not run */
+    double ms_iter_median;                    /* CG: median ms per iteration (over polling batches) */
+    double ms_total;
+} ptv_pressure_stats;
+
 /* Library / device management. */
 int ptv_version(void);
 /* sizeof(ptv_particles, ptv_grid, ptv_knn_params, ptv_stats, ptv_rbf_params, ptv_div_params):
@@ -475,6 +521,9 @@ int ptv_abi_sizes7(int64_t out2[2]);
  * library that has this symbol has the distance transform and alignment score entry points
  * (PTV_API_VERSION stays 11). */
 int ptv_abi_sizes8(int64_t out4[4]);
+/* sizeof(ptv_pressure_params, ptv_pressure_stats): the same self-check.  A library that has this
+ * symbol has the pressure recovery entry points (PTV_API_VERSION stays 11). */
+int ptv_abi_sizes9(int64_t out2[2]);
 const char *ptv_last_error(void);
 int ptv_device_count(int *out);
 int ptv_init(int device, ptv_ctx **out);
@@ -738,6 +787,57 @@ int ptv_align_score(ptv_ctx *ctx, const ptv_align_params *prm, const double *poi
  * (NULL = the ctx's own); synchronises (the records are returned). */
 int ptv_align_score_dev(ptv_ctx *ctx, const ptv_align_params *prm, const double *points, const double *dt,
                         const double *offsets, void *stream, ptv_align_record *records, double *ms);
+
+/*
+ * Force field, host buffers: F = mu * laplacian_mask_aware(U, V, W) - rho * advection, written at
+ * every voxel.  st (may be NULL) receives n_fluid, the four sums and ms_force.
+ */
+int ptv_force_field(ptv_ctx *ctx, const ptv_pressure_params *prm, const double *U, const double *V, const double *W,
+                    double *Fx, double *Fy, double *Fz, ptv_pressure_stats *st);
+
+/* Same on device pointers (prm->fluid_mask too), enqueued on `stream` (NULL = the ctx's own);
+ * synchronises (the sums are returned).  The outputs must not alias the inputs. */
+int ptv_force_field_dev(ptv_ctx *ctx, const ptv_pressure_params *prm, const double *U, const double *V,
+                        const double *W, double *Fx, double *Fy, double *Fz, void *stream, ptv_pressure_stats *st);
+
+/* Force divergence under prm->wall_bc, host buffers; D is written at every voxel (under
+ * PTV_WALL_INHOMOGENEOUS solid voxels next to fluid get non-zero values, as in the reference). */
+int ptv_force_divergence(ptv_ctx *ctx, const ptv_pressure_params *prm, const double *Fx, const double *Fy,
+                         const double *Fz, double *D);
+
+/* Same on device pointers, enqueued on `stream`; does not synchronise.  D must not alias F. */
+int ptv_force_divergence_dev(ptv_ctx *ctx, const ptv_pressure_params *prm, const double *Fx, const double *Fy,
+                             const double *Fz, double *D, void *stream);
+
+/*
+ * Poisson solve, host buffers.  The right-hand side is rhs, or, when rhs is NULL, the divergence
+ * of the force field Fx, Fy, Fz under prm->wall_bc.  dirichlet: a uint8 grid (nonzero = the voxel
+ * is fixed to 0; only fluid voxels count) selects CG; NULL selects LSQR on b - mean(b).  X is 0 at
+ * solid and Dirichlet voxels.  A NaN in the right-hand side of the CG solve gives NaN at every
+ * fluid voxel, info = itn = maxiter (what scipy's recurrence returns).
+ */
+int ptv_poisson_solve(ptv_ctx *ctx, const ptv_pressure_params *prm, const double *rhs, const double *Fx,
+                      const double *Fy, const double *Fz, const uint8_t *dirichlet, double *X,
+                      ptv_pressure_stats *st);
+
+/* Same on device pointers, enqueued on `stream`; synchronises.  X may alias rhs. */
+int ptv_poisson_solve_dev(ptv_ctx *ctx, const ptv_pressure_params *prm, const double *rhs, const double *Fx,
+                          const double *Fy, const double *Fz, const uint8_t *dirichlet, double *X, void *stream,
+                          ptv_pressure_stats *st);
+
+/*
+ * The whole chain of compute_pressure_field, resident on the device: one copy in (U, V, W, the
+ * mask), the force field, its divergence, the solve, one copy out (P).  The Dirichlet set is the
+ * fluid voxels of the plane prm->anchor and prm->flow_direction select (outlet = the last z plane
+ * for a positive flow; auto takes the sign of sum w over the fluid voxels, >= 0 is positive);
+ * PTV_ANCHOR_NONE runs the LSQR solve.
+ */
+int ptv_pressure_recover(ptv_ctx *ctx, const ptv_pressure_params *prm, const double *U, const double *V,
+                         const double *W, double *P, ptv_pressure_stats *st);
+
+/* Same on device pointers, enqueued on `stream`; synchronises.  P may alias none of the inputs. */
+int ptv_pressure_recover_dev(ptv_ctx *ctx, const ptv_pressure_params *prm, const double *U, const double *V,
+                             const double *W, double *P, void *stream, ptv_pressure_stats *st);
 
 /*
  * Last-launch k-NN kernel duration in ms (hipEvent pair recorded around the

@@ -7,7 +7,9 @@ path (next to the caller's script), it is loaded under a private name and every 
 names is re-exported; only ``compute_consistent_divergence`` (physics.py:6-53) is replaced
 by the MI355X kernel, also inside the reference module, so that the cleaning loops
 (physics.py:173, :193-194) call the GPU stencil too (bit-identical results).  Without the
-reference module (the GPU box), only the divergence is provided.
+reference module (the GPU box), the divergence and the GPU ``compute_force_divergence`` and
+``solve_poisson`` (physics.py:211-345) are provided; with the reference module present those two
+stay the host's.
 
 Opt-in: with ``PTV_GPU_CLEAN=1`` in the environment, ``clean_divergence_projection`` and
 ``apply_consistent_correction`` (physics.py:110-209) are replaced the same way, here and inside the
@@ -72,3 +74,6 @@ if _GPU_CLEAN_VARIATIONAL:
     clean_divergence_variational = _gpu.clean_divergence_variational
     if _ref is not None:
         _ref.clean_divergence_variational = _gpu.clean_divergence_variational
+if _ref is None:
+    compute_force_divergence = _gpu.compute_force_divergence
+    solve_poisson = _gpu.solve_poisson

@@ -179,6 +179,30 @@ class DragStats(C.Structure):
 DRAG_RECORD = np.dtype([("count", np.int64), ("sum_p", np.float64), ("sum_u", np.float64), ("sum_v", np.float64),
                         ("sum_w", np.float64)])
 
+WALL_BC = {"zero-neumann": 0, "inhomogeneous": 1}  # PTV_WALL_*
+ANCHOR = {"none": 0, "outlet": 1, "inlet": 2}      # PTV_ANCHOR_*
+FLOW_DIRECTION = {"auto": 0, "positive": 1, "negative": -1}
+
+
+class PressureParams(C.Structure):
+    _fields_ = [("nx", C.c_int64), ("ny", C.c_int64), ("nz", C.c_int64), ("dx", C.c_double), ("dy", C.c_double),
+                ("dz", C.c_double), ("mu", C.c_double), ("rho", C.c_double), ("wall_bc", C.c_int),
+                ("anchor", C.c_int), ("flow_direction", C.c_int), ("maxiter", C.c_int), ("rtol", C.c_double),
+                ("lsqr_damp", C.c_double), ("lsqr_atol", C.c_double), ("lsqr_btol", C.c_double),
+                ("lsqr_iter_lim", C.c_int), ("fluid_mask", _u8p)]
+
+
+class PressureStats(C.Structure):
+    _fields_ = [("n_fluid", C.c_int64), ("n_dirichlet", C.c_int64), ("itn", C.c_int32), ("info", C.c_int32),
+                ("solver", C.c_int32), ("anchor_plane", C.c_int32), ("bnorm", C.c_double), ("rnorm", C.c_double),
+                ("sum_abs_fx", C.c_double), ("sum_abs_fy", C.c_double), ("sum_abs_fz", C.c_double),
+                ("sum_w", C.c_double), ("ms_force", C.c_double), ("ms_divergence", C.c_double),
+                ("ms_solve", C.c_double), ("ms_iter_median", C.c_double), ("ms_total", C.c_double)]
+
+    def as_dict(self):
+        return {f: getattr(self, f) for f, _ in self._fields_}
+
+
 class EdtParams(C.Structure):
     _fields_ = [("nx", C.c_int64), ("ny", C.c_int64), ("nz", C.c_int64), ("keep_distance", C.c_int)]
 
@@ -302,6 +326,20 @@ EXPORTS = {
     "ptv_edt_dev": (C.c_int, [C.c_void_p, C.POINTER(EdtParams)] + [C.c_void_p] * 4 + [C.POINTER(EdtStats)]),
     "ptv_align_score": (C.c_int, [C.c_void_p, C.POINTER(AlignParams)] + [C.c_void_p] * 4 + [_dp]),
     "ptv_align_score_dev": (C.c_int, [C.c_void_p, C.POINTER(AlignParams)] + [C.c_void_p] * 5 + [_dp]),
+    "ptv_abi_sizes9": (C.c_int, [C.POINTER(C.c_int64)]),
+    "ptv_force_field": (C.c_int, [C.c_void_p, C.POINTER(PressureParams)] + [_dp] * 6 + [C.POINTER(PressureStats)]),
+    "ptv_force_field_dev": (C.c_int, [C.c_void_p, C.POINTER(PressureParams)] + [_dp] * 6 +
+                            [C.c_void_p, C.POINTER(PressureStats)]),
+    "ptv_force_divergence": (C.c_int, [C.c_void_p, C.POINTER(PressureParams)] + [_dp] * 4),
+    "ptv_force_divergence_dev": (C.c_int, [C.c_void_p, C.POINTER(PressureParams)] + [_dp] * 4 + [C.c_void_p]),
+    "ptv_poisson_solve": (C.c_int, [C.c_void_p, C.POINTER(PressureParams)] + [_dp] * 4 + [_u8p, _dp,
+                                                                                           C.POINTER(PressureStats)]),
+    "ptv_poisson_solve_dev": (C.c_int, [C.c_void_p, C.POINTER(PressureParams)] + [_dp] * 4 +
+                              [_u8p, _dp, C.c_void_p, C.POINTER(PressureStats)]),
+    "ptv_pressure_recover": (C.c_int, [C.c_void_p, C.POINTER(PressureParams)] + [_dp] * 4 +
+                             [C.POINTER(PressureStats)]),
+    "ptv_pressure_recover_dev": (C.c_int, [C.c_void_p, C.POINTER(PressureParams)] + [_dp] * 4 +
+                                 [C.c_void_p, C.POINTER(PressureStats)]),
     "ptv_last_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     "ptv_debug_stamps": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double)]),
 }
@@ -425,6 +463,13 @@ def abi_sizes8():
     out = (C.c_int64 * 4)()
     check(lib().ptv_abi_sizes8(out))
     return list(out), [C.sizeof(EdtParams), C.sizeof(EdtStats), C.sizeof(AlignParams), C.sizeof(AlignRecord)]
+
+
+def abi_sizes9():
+    """(C sizeof, ctypes sizeof) of ptv_pressure_params and ptv_pressure_stats."""
+    out = (C.c_int64 * 2)()
+    check(lib().ptv_abi_sizes9(out))
+    return list(out), [C.sizeof(PressureParams), C.sizeof(PressureStats)]
 
 
 def edt_check_shape(shape):
@@ -1157,6 +1202,110 @@ class Context:
         out = (C.c_double * 3)()
         check(lib().ptv_gradient_sums_dev(self.h, C.byref(prm), C.c_void_p(ptr), C.c_void_p(stream or 0), out))
         return [float(x) for x in out]
+
+    # -- pressure recovery (velocity_analysis.py:190-330, physics.py:211-345) ----
+    @staticmethod
+    def _mask_bytes(mask, shape):
+        """A bool or uint8 (any non-zero byte = fluid) mask as contiguous uint8 of ``shape``."""
+        mk = np.asarray(mask)
+        mk = mk.view(np.uint8) if mk.dtype == np.bool_ else mk.astype(np.uint8, copy=False)
+        return np.ascontiguousarray(mk).reshape(shape)
+
+    @staticmethod
+    def _pressure_params(shape, mask_ptr, dx, dy, dz, mu=0.0, rho=0.0, wall_bc="zero-neumann", anchor="none",
+                         flow_direction="auto", rtol=1e-10, maxiter=3000, damp=1e-8, atol=1e-10, btol=1e-10,
+                         iter_lim=3000):
+        nz, ny, nx = shape
+        return PressureParams(nx, ny, nz, float(dx), float(dy), float(dz), float(mu), float(rho), WALL_BC[wall_bc],
+                              ANCHOR[anchor], FLOW_DIRECTION[flow_direction], int(maxiter), float(rtol), float(damp),
+                              float(atol), float(btol), int(iter_lim), C.cast(C.c_void_p(mask_ptr), _u8p))
+
+    def force_field(self, u, v, w, fluid_mask, dx, dy, dz, mu, rho=0.0):
+        """``mu * laplacian_mask_aware(vel) - rho * advection`` of float64 (nz, ny, nx) host fields
+        (velocity_analysis.py:210-289); returns ``((fx, fy, fz), stats dict)``."""
+        f = [np.ascontiguousarray(a, dtype=np.float64) for a in (u, v, w)]
+        mk = self._mask_bytes(fluid_mask, f[0].shape)
+        prm = self._pressure_params(f[0].shape, mk.ctypes.data, dx, dy, dz, mu, rho)
+        out = [np.empty_like(a) for a in f]
+        st = PressureStats()
+        check(lib().ptv_force_field(self.h, C.byref(prm), *[as_dp(a) for a in f], *[as_dp(a) for a in out],
+                                    C.byref(st)))
+        return tuple(out), st.as_dict()
+
+    def force_field_dev(self, nx, ny, nz, ptrs, mask_ptr, out_ptrs, dx, dy, dz, mu, rho=0.0, stream=0):
+        """Device-pointer force field (the outputs must not alias the inputs); returns the stats dict."""
+        prm = self._pressure_params((nz, ny, nx), mask_ptr, dx, dy, dz, mu, rho)
+        st = PressureStats()
+        check(lib().ptv_force_field_dev(self.h, C.byref(prm), *[dev_dp(p) for p in ptrs],
+                                        *[dev_dp(p) for p in out_ptrs], C.c_void_p(stream or 0), C.byref(st)))
+        return st.as_dict()
+
+    def force_divergence(self, fx, fy, fz, fluid_mask, dx, dy, dz, wall_bc="zero-neumann"):
+        """physics.py:211-262 for float64 host fields: the divergence at every voxel."""
+        f = [np.ascontiguousarray(a, dtype=np.float64) for a in (fx, fy, fz)]
+        mk = self._mask_bytes(fluid_mask, f[0].shape)
+        prm = self._pressure_params(f[0].shape, mk.ctypes.data, dx, dy, dz, wall_bc=wall_bc)
+        d = np.empty_like(f[0])
+        check(lib().ptv_force_divergence(self.h, C.byref(prm), *[as_dp(a) for a in f], as_dp(d)))
+        return d
+
+    def force_divergence_dev(self, nx, ny, nz, ptrs, mask_ptr, out_ptr, dx, dy, dz, wall_bc="zero-neumann", stream=0):
+        """Device-pointer force divergence; enqueues only (synchronise the stream to read it)."""
+        prm = self._pressure_params((nz, ny, nx), mask_ptr, dx, dy, dz, wall_bc=wall_bc)
+        check(lib().ptv_force_divergence_dev(self.h, C.byref(prm), *[dev_dp(p) for p in ptrs], dev_dp(out_ptr),
+                                             C.c_void_p(stream or 0)))
+
+    def poisson_solve(self, fluid_mask, dx, dy, dz, rhs=None, force_field=None, dirichlet=None,
+                      wall_bc="inhomogeneous", **solver):
+        """physics.py:264-345 for host arrays: ``rhs`` or the divergence of ``force_field`` under
+        ``wall_bc``; a ``dirichlet`` grid (fixed to 0) selects CG (``rtol``, ``maxiter``), None LSQR
+        (``damp``, ``atol``, ``btol``, ``iter_lim``).  Returns ``(x, stats dict)``."""
+        src = [rhs] if rhs is not None else list(force_field)
+        src = [np.ascontiguousarray(a, dtype=np.float64) for a in src]
+        shape = src[0].shape
+        mk = self._mask_bytes(fluid_mask, shape)
+        dm = self._mask_bytes(dirichlet, shape) if dirichlet is not None else None
+        prm = self._pressure_params(shape, mk.ctypes.data, dx, dy, dz, wall_bc=wall_bc, **solver)
+        x = np.empty(shape, dtype=np.float64)
+        st = PressureStats()
+        ptrs = [as_dp(src[0]), None, None, None] if rhs is not None else [None] + [as_dp(a) for a in src]
+        check(lib().ptv_poisson_solve(self.h, C.byref(prm), *ptrs, dm.ctypes.data_as(_u8p) if dm is not None else None,
+                                      as_dp(x), C.byref(st)))
+        return x, st.as_dict()
+
+    def poisson_solve_dev(self, nx, ny, nz, mask_ptr, out_ptr, dx, dy, dz, rhs_ptr=0, force_ptrs=None,
+                          dirichlet_ptr=0, wall_bc="inhomogeneous", stream=0, **solver):
+        """Device-pointer Poisson solve (``out_ptr`` may be ``rhs_ptr``); returns the stats dict."""
+        prm = self._pressure_params((nz, ny, nx), mask_ptr, dx, dy, dz, wall_bc=wall_bc, **solver)
+        st = PressureStats()
+        ptrs = [dev_dp(rhs_ptr) if rhs_ptr else None] + [dev_dp(p) if p else None for p in (force_ptrs or (0, 0, 0))]
+        check(lib().ptv_poisson_solve_dev(self.h, C.byref(prm), *ptrs,
+                                          C.cast(C.c_void_p(dirichlet_ptr), _u8p) if dirichlet_ptr else None,
+                                          dev_dp(out_ptr), C.c_void_p(stream or 0), C.byref(st)))
+        return st.as_dict()
+
+    def pressure_recover(self, u, v, w, fluid_mask, dx, dy, dz, mu, rho=0.0, wall_bc="zero-neumann", anchor="outlet",
+                         flow_direction="auto", **solver):
+        """The whole chain of compute_pressure_field for float64 host fields, resident on the device:
+        one copy in, one copy out.  Returns ``(p, stats dict)``."""
+        f = [np.ascontiguousarray(a, dtype=np.float64) for a in (u, v, w)]
+        mk = self._mask_bytes(fluid_mask, f[0].shape)
+        prm = self._pressure_params(f[0].shape, mk.ctypes.data, dx, dy, dz, mu, rho, wall_bc, anchor, flow_direction,
+                                    **solver)
+        p = np.empty_like(f[0])
+        st = PressureStats()
+        check(lib().ptv_pressure_recover(self.h, C.byref(prm), *[as_dp(a) for a in f], as_dp(p), C.byref(st)))
+        return p, st.as_dict()
+
+    def pressure_recover_dev(self, nx, ny, nz, ptrs, mask_ptr, out_ptr, dx, dy, dz, mu, rho=0.0,
+                             wall_bc="zero-neumann", anchor="outlet", flow_direction="auto", stream=0, **solver):
+        """Device-pointer chain (fields, mask and the pressure resident in HBM); returns the stats dict."""
+        prm = self._pressure_params((nz, ny, nx), mask_ptr, dx, dy, dz, mu, rho, wall_bc, anchor, flow_direction,
+                                    **solver)
+        st = PressureStats()
+        check(lib().ptv_pressure_recover_dev(self.h, C.byref(prm), *[dev_dp(p) for p in ptrs], dev_dp(out_ptr),
+                                             C.c_void_p(stream or 0), C.byref(st)))
+        return st.as_dict()
 
     # -- distance transform and alignment score (auto_align.py:10-62) ----
     def edt(self, mask, want_d2=True, want_distance=True, keep_distance=False):

@@ -118,6 +118,16 @@ int ptv_abi_sizes8(int64_t out4[4]) {
     return PTV_OK;
 }
 
+int ptv_abi_sizes9(int64_t out2[2]) {
+    if (!out2) {
+        set_error("ptv_abi_sizes9: out is NULL");
+        return PTV_E_ARG;
+    }
+    out2[0] = (int64_t)sizeof(ptv_pressure_params);
+    out2[1] = (int64_t)sizeof(ptv_pressure_stats);
+    return PTV_OK;
+}
+
 const char *ptv_last_error(void) { return g_last_error.c_str(); }
 
 int ptv_device_count(int *out) {
@@ -952,6 +962,316 @@ int ptv_variational_apply(ptv_ctx *c, const ptv_variational_params *prm, const d
                                c->var.part, s));
     double *dst[3] = {yu, yv, yw};
     for (int i = 0; i < 3; ++i) PTV_HIP(hipMemcpyAsync(dst[i], f[3 + i], n * sizeof(double), hipMemcpyDeviceToHost, s));
+    PTV_HIP(hipStreamSynchronize(s));
+    return PTV_OK;
+}
+
+// ---- pressure recovery (ptv_pressure.hip; the LSQR solve is ptv_clean.hip's) ----
+// every argument check of the family, before any copy or launch
+static int press_check(ptv_ctx *c, const ptv_pressure_params *prm, PressGrid &g) {
+    if (!c || !prm) {
+        set_error("NULL context/params");
+        return PTV_E_ARG;
+    }
+    if (!prm->fluid_mask) {
+        set_error("pressure: the fluid mask is required");
+        return PTV_E_ARG;
+    }
+    if (prm->nx <= 0 || prm->ny <= 0 || prm->nz <= 0 || prm->nx > (1 << 30) || prm->ny > (1 << 30) ||
+        prm->nz > (1 << 30) || prm->nx * prm->ny * prm->nz > 0x7fff0000LL) {
+        set_error("pressure: dimensions must be positive, with fewer than 2^31 voxels");
+        return PTV_E_ARG;
+    }
+    for (double h : {prm->dx, prm->dy, prm->dz}) {
+        if (!(h > 0.0) || !std::isfinite(h)) {
+            set_error("pressure: spacings must be positive finite numbers");
+            return PTV_E_ARG;
+        }
+    }
+    if (!std::isfinite(prm->mu) || !std::isfinite(prm->rho)) {
+        set_error("pressure: mu and rho must be finite");
+        return PTV_E_ARG;
+    }
+    if (prm->wall_bc != PTV_WALL_ZERO_NEUMANN && prm->wall_bc != PTV_WALL_INHOMOGENEOUS) {
+        set_error("pressure: wall_bc must be PTV_WALL_ZERO_NEUMANN or PTV_WALL_INHOMOGENEOUS");
+        return PTV_E_ARG;
+    }
+    if (prm->anchor < PTV_ANCHOR_NONE || prm->anchor > PTV_ANCHOR_INLET || prm->flow_direction < -1 ||
+        prm->flow_direction > 1) {
+        set_error("pressure: anchor must be PTV_ANCHOR_* and flow_direction -1, 0 or 1");
+        return PTV_E_ARG;
+    }
+    if (!std::isfinite(prm->rtol) || prm->maxiter < 0 || prm->lsqr_iter_lim < 0 || !(prm->lsqr_damp >= 0.0) ||
+        !(prm->lsqr_atol >= 0.0) || !(prm->lsqr_btol >= 0.0)) {
+        set_error("pressure: rtol must be finite; maxiter and the LSQR settings non-negative");
+        return PTV_E_ARG;
+    }
+    g.nx = (int)prm->nx;
+    g.ny = (int)prm->ny;
+    g.nz = (int)prm->nz;
+    g.dx = prm->dx;
+    g.dy = prm->dy;
+    g.dz = prm->dz;
+    return PTV_OK;
+}
+
+static int press_rho_check(const ptv_pressure_params *prm) {
+    if (prm->rho > 0.0 && (prm->nx < 2 || prm->ny < 2 || prm->nz < 2)) {
+        set_error("pressure: rho > 0 needs at least 2 voxels along every axis (np.gradient)");
+        return PTV_E_ARG;
+    }
+    return PTV_OK;
+}
+
+// CG with a Dirichlet grid, LSQR without one; all pointers device memory
+static int press_solve(ptv_ctx *c, const ptv_pressure_params *prm, const PressGrid &g, const uint8_t *M,
+                       const double *rhs, const uint8_t *Dir, double *X, hipStream_t s, ptv_pressure_stats &out) {
+    if (Dir) return press_cg(c->press, g, prm->rtol, prm->maxiter, M, Dir, rhs, X, s, &out);
+    const CleanGrid cg{g.nx, g.ny, g.nz, g.dx, g.dy, g.dz};
+    const CleanSolve sv{0, prm->lsqr_damp, prm->lsqr_atol, prm->lsqr_btol, prm->lsqr_iter_lim};
+    CleanRhsResult r{};
+    PTV_TRY(clean_solve_rhs(c->clean, cg, sv, M, rhs, X, s, &r));
+    out.solver = 1;
+    out.n_fluid = r.n_fluid;
+    out.n_dirichlet = 0;
+    out.itn = r.itn;
+    out.info = r.istop;
+    out.bnorm = r.bnorm;
+    out.rnorm = r.rnorm;
+    out.ms_solve = r.ms_solve;
+    out.ms_iter_median = r.ms_iter_median;
+    return PTV_OK;
+}
+
+static size_t press_n(const ptv_pressure_params *prm) { return (size_t)(prm->nx * prm->ny * prm->nz); }
+
+// host grids -> c->press_fld[first + i], the mask -> c->mask
+static int press_upload(ptv_ctx *c, const ptv_pressure_params *prm, const double *const *src, int nf, int first,
+                        hipStream_t s) {
+    const size_t n = press_n(prm);
+    for (int i = 0; i < nf; ++i) {
+        PTV_TRY(c->press_fld[first + i].ensure(n));
+        PTV_HIP(hipMemcpyAsync(c->press_fld[first + i].p, src[i], n * sizeof(double), hipMemcpyHostToDevice, s));
+    }
+    PTV_TRY(c->mask.ensure(n));
+    PTV_HIP(hipMemcpyAsync(c->mask.p, prm->fluid_mask, n, hipMemcpyHostToDevice, s));
+    return PTV_OK;
+}
+
+int ptv_force_field_dev(ptv_ctx *c, const ptv_pressure_params *prm, const double *U, const double *V, const double *W,
+                        double *Fx, double *Fy, double *Fz, void *stream, ptv_pressure_stats *st) {
+    PressGrid g{};
+    PTV_TRY(press_check(c, prm, g));
+    PTV_TRY(press_rho_check(prm));
+    if (!U || !V || !W || !Fx || !Fy || !Fz) {
+        set_error("force_field: NULL field or output");
+        return PTV_E_ARG;
+    }
+    PTV_HIP(hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    ptv_pressure_stats out{};
+    out.anchor_plane = -1;
+    PTV_TRY(press_force(c->press, g, prm->mu, prm->rho, prm->fluid_mask, U, V, W, Fx, Fy, Fz, s, &out));
+    out.ms_total = out.ms_force;
+    if (st) *st = out;
+    return PTV_OK;
+}
+
+int ptv_force_field(ptv_ctx *c, const ptv_pressure_params *prm, const double *U, const double *V, const double *W,
+                    double *Fx, double *Fy, double *Fz, ptv_pressure_stats *st) {
+    PressGrid g{};
+    PTV_TRY(press_check(c, prm, g));
+    PTV_TRY(press_rho_check(prm));
+    if (!U || !V || !W || !Fx || !Fy || !Fz) {
+        set_error("force_field: NULL field or output");
+        return PTV_E_ARG;
+    }
+    PTV_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const size_t n = press_n(prm);
+    const double *src[3] = {U, V, W};
+    PTV_TRY(press_upload(c, prm, src, 3, 0, s));
+    for (int i = 3; i < 6; ++i) PTV_TRY(c->press_fld[i].ensure(n));
+    ptv_pressure_params dp = *prm;
+    dp.fluid_mask = c->mask.p;
+    PTV_TRY(ptv_force_field_dev(c, &dp, c->press_fld[0].p, c->press_fld[1].p, c->press_fld[2].p, c->press_fld[3].p,
+                                c->press_fld[4].p, c->press_fld[5].p, s, st));
+    double *dst[3] = {Fx, Fy, Fz};
+    for (int i = 0; i < 3; ++i)
+        PTV_HIP(hipMemcpyAsync(dst[i], c->press_fld[3 + i].p, n * sizeof(double), hipMemcpyDeviceToHost, s));
+    PTV_HIP(hipStreamSynchronize(s));
+    return PTV_OK;
+}
+
+int ptv_force_divergence_dev(ptv_ctx *c, const ptv_pressure_params *prm, const double *Fx, const double *Fy,
+                             const double *Fz, double *D, void *stream) {
+    PressGrid g{};
+    PTV_TRY(press_check(c, prm, g));
+    if (!Fx || !Fy || !Fz || !D) {
+        set_error("force_divergence: NULL field or output");
+        return PTV_E_ARG;
+    }
+    PTV_HIP(hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    return press_divergence(g, prm->wall_bc == PTV_WALL_INHOMOGENEOUS, prm->fluid_mask, Fx, Fy, Fz, D, s);
+}
+
+int ptv_force_divergence(ptv_ctx *c, const ptv_pressure_params *prm, const double *Fx, const double *Fy,
+                         const double *Fz, double *D) {
+    PressGrid g{};
+    PTV_TRY(press_check(c, prm, g));
+    if (!Fx || !Fy || !Fz || !D) {
+        set_error("force_divergence: NULL field or output");
+        return PTV_E_ARG;
+    }
+    PTV_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const size_t n = press_n(prm);
+    const double *src[3] = {Fx, Fy, Fz};
+    PTV_TRY(press_upload(c, prm, src, 3, 3, s));
+    PTV_TRY(c->press_fld[6].ensure(n));
+    PTV_TRY(press_divergence(g, prm->wall_bc == PTV_WALL_INHOMOGENEOUS, c->mask.p, c->press_fld[3].p,
+                             c->press_fld[4].p, c->press_fld[5].p, c->press_fld[6].p, s));
+    PTV_HIP(hipMemcpyAsync(D, c->press_fld[6].p, n * sizeof(double), hipMemcpyDeviceToHost, s));
+    PTV_HIP(hipStreamSynchronize(s));
+    return PTV_OK;
+}
+
+int ptv_poisson_solve_dev(ptv_ctx *c, const ptv_pressure_params *prm, const double *rhs, const double *Fx,
+                          const double *Fy, const double *Fz, const uint8_t *dirichlet, double *X, void *stream,
+                          ptv_pressure_stats *st) {
+    PressGrid g{};
+    PTV_TRY(press_check(c, prm, g));
+    if (!X || (!rhs && (!Fx || !Fy || !Fz))) {
+        set_error("poisson_solve: NULL output, or neither a right-hand side nor a force field");
+        return PTV_E_ARG;
+    }
+    PTV_HIP(hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    ptv_pressure_stats out{};
+    out.anchor_plane = -1;
+    PTV_TRY(c->ev_press[0].record(s));
+    if (!rhs) {
+        PTV_TRY(c->press.rhs.ensure(press_n(prm)));
+        PTV_TRY(press_divergence(g, prm->wall_bc == PTV_WALL_INHOMOGENEOUS, prm->fluid_mask, Fx, Fy, Fz,
+                                 c->press.rhs.p, s));
+        rhs = c->press.rhs.p;
+    }
+    PTV_TRY(press_solve(c, prm, g, prm->fluid_mask, rhs, dirichlet, X, s, out));
+    PTV_TRY(c->ev_press[3].record(s));
+    PTV_HIP(hipStreamSynchronize(s));
+    float ms = 0.f;
+    PTV_HIP(hipEventElapsedTime(&ms, c->ev_press[0], c->ev_press[3]));
+    out.ms_total = ms;
+    if (st) *st = out;
+    return PTV_OK;
+}
+
+int ptv_poisson_solve(ptv_ctx *c, const ptv_pressure_params *prm, const double *rhs, const double *Fx,
+                      const double *Fy, const double *Fz, const uint8_t *dirichlet, double *X,
+                      ptv_pressure_stats *st) {
+    PressGrid g{};
+    PTV_TRY(press_check(c, prm, g));
+    if (!X || (!rhs && (!Fx || !Fy || !Fz))) {
+        set_error("poisson_solve: NULL output, or neither a right-hand side nor a force field");
+        return PTV_E_ARG;
+    }
+    PTV_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const size_t n = press_n(prm);
+    const double *src[3] = {Fx, Fy, Fz};
+    if (rhs) {
+        src[0] = rhs;
+        PTV_TRY(press_upload(c, prm, src, 1, 6, s));
+    } else {
+        PTV_TRY(press_upload(c, prm, src, 3, 3, s));
+        PTV_TRY(c->press_fld[6].ensure(n));
+    }
+    if (dirichlet) {
+        PTV_TRY(c->press_dir.ensure(n));
+        PTV_HIP(hipMemcpyAsync(c->press_dir.p, dirichlet, n, hipMemcpyHostToDevice, s));
+    }
+    ptv_pressure_params dp = *prm;
+    dp.fluid_mask = c->mask.p;
+    double *x = c->press_fld[6].p;
+    PTV_TRY(ptv_poisson_solve_dev(c, &dp, rhs ? x : nullptr, c->press_fld[3].p, c->press_fld[4].p, c->press_fld[5].p,
+                                  dirichlet ? c->press_dir.p : nullptr, x, s, st));
+    PTV_HIP(hipMemcpyAsync(X, x, n * sizeof(double), hipMemcpyDeviceToHost, s));
+    PTV_HIP(hipStreamSynchronize(s));
+    return PTV_OK;
+}
+
+int ptv_pressure_recover_dev(ptv_ctx *c, const ptv_pressure_params *prm, const double *U, const double *V,
+                             const double *W, double *P, void *stream, ptv_pressure_stats *st) {
+    PressGrid g{};
+    PTV_TRY(press_check(c, prm, g));
+    PTV_TRY(press_rho_check(prm));
+    if (!U || !V || !W || !P) {
+        set_error("pressure_recover: NULL field or output");
+        return PTV_E_ARG;
+    }
+    PTV_HIP(hipSetDevice(c->device));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    const size_t n = press_n(prm);
+    PTV_TRY(c->press.f.ensure(3 * n));
+    PTV_TRY(c->press.rhs.ensure(n));
+    PTV_TRY(c->press.dir.ensure(n));
+    double *F = c->press.f.p;
+    const uint8_t *M = prm->fluid_mask;
+    ptv_pressure_stats out{};
+    out.anchor_plane = -1;
+    PTV_TRY(c->ev_press[0].record(s));
+    PTV_TRY(press_force(c->press, g, prm->mu, prm->rho, M, U, V, W, F, F + n, F + 2 * n, s, &out));
+    if (out.n_fluid == 0) {  // physics.py:274-276
+        PTV_HIP(hipMemsetAsync(P, 0, n * sizeof(double), s));
+        PTV_HIP(hipStreamSynchronize(s));
+        if (st) *st = out;
+        return PTV_OK;
+    }
+    PTV_TRY(c->ev_press[1].record(s));
+    PTV_TRY(press_divergence(g, prm->wall_bc == PTV_WALL_INHOMOGENEOUS, M, F, F + n, F + 2 * n, c->press.rhs.p, s));
+    PTV_TRY(c->ev_press[2].record(s));
+    const uint8_t *Dir = nullptr;
+    if (prm->anchor != PTV_ANCHOR_NONE) {
+        // velocity_analysis.py:304-321: np.mean(w[mask]) >= 0 has the sign of the sum
+        const bool positive = prm->flow_direction == 1 || (prm->flow_direction == 0 && out.sum_w >= 0.0);
+        const bool last = (prm->anchor == PTV_ANCHOR_OUTLET) == positive;
+        out.anchor_plane = last ? g.nz - 1 : 0;
+        PTV_TRY(press_anchor_plane(g, out.anchor_plane, M, c->press.dir.p, s));
+        Dir = c->press.dir.p;
+    }
+    PTV_TRY(press_solve(c, prm, g, M, c->press.rhs.p, Dir, P, s, out));
+    PTV_TRY(c->ev_press[3].record(s));
+    PTV_HIP(hipStreamSynchronize(s));
+    float ms = 0.f;
+    PTV_HIP(hipEventElapsedTime(&ms, c->ev_press[1], c->ev_press[2]));
+    out.ms_divergence = ms;
+    PTV_HIP(hipEventElapsedTime(&ms, c->ev_press[0], c->ev_press[3]));
+    out.ms_total = ms;
+    if (st) *st = out;
+    return PTV_OK;
+}
+
+int ptv_pressure_recover(ptv_ctx *c, const ptv_pressure_params *prm, const double *U, const double *V,
+                         const double *W, double *P, ptv_pressure_stats *st) {
+    PressGrid g{};
+    PTV_TRY(press_check(c, prm, g));
+    PTV_TRY(press_rho_check(prm));
+    if (!U || !V || !W || !P) {
+        set_error("pressure_recover: NULL field or output");
+        return PTV_E_ARG;
+    }
+    PTV_HIP(hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const size_t n = press_n(prm);
+    const double *src[3] = {U, V, W};
+    PTV_TRY(press_upload(c, prm, src, 3, 0, s));
+    PTV_TRY(c->press_fld[6].ensure(n));
+    ptv_pressure_params dp = *prm;
+    dp.fluid_mask = c->mask.p;
+    PTV_TRY(ptv_pressure_recover_dev(c, &dp, c->press_fld[0].p, c->press_fld[1].p, c->press_fld[2].p,
+                                     c->press_fld[6].p, s, st));
+    PTV_HIP(hipMemcpyAsync(P, c->press_fld[6].p, n * sizeof(double), hipMemcpyDeviceToHost, s));
     PTV_HIP(hipStreamSynchronize(s));
     return PTV_OK;
 }

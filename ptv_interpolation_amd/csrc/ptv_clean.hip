@@ -625,6 +625,43 @@ int launch_clean_correction(const CleanGrid &g, const uint8_t *M, const double *
     return PTV_OK;
 }
 
+int clean_solve_rhs(CleanWork &wk, const CleanGrid &g, const CleanSolve &sv, const uint8_t *M, const double *rhs,
+                    double *X, hipStream_t s, CleanRhsResult *res) {
+    CleanArgs a{};
+    PTV_TRY(make_args(g, a));
+    if (sv.iter_lim < 0 || !(sv.damp >= 0.0) || !(sv.atol >= 0.0) || !(sv.btol >= 0.0)) {
+        set_error("clean: iter_lim, damp, atol and btol must be non-negative");
+        return PTV_E_ARG;
+    }
+    const size_t n = a.n, nbytes = n * sizeof(double);
+    for (DevBuf<double> *b : {&wk.u, &wk.v, &wk.w, &wk.x, &wk.div}) PTV_TRY(b->ensure(n));
+    const bool vec2 = a.nx % 2 == 0 && aligned(M, 2);  // every vector is hipMalloc-aligned scratch
+    const unsigned nb = blocks_for(a.n, vec2 ? 2 : 1);
+    PTV_TRY(wk.part.ensure(3 * (size_t)nb));
+    PTV_TRY(wk.state.ensure(kStateLen));
+    PTV_TRY(wk.rep.ensure(kRepLen));
+    PTV_TRY(wk.h_state.ensure(3 * kStateLen + kRepLen));
+    double *h_final = wk.h_state.p + 2 * kStateLen;
+    Solver sol{wk, a, LsqrCfg{sv.damp, sv.atol, sv.btol, 1.0 / 1e8, sv.iter_lim}, M, s, vec2, nb};
+    PTV_HIP(hipMemsetAsync(wk.state.p, 0, kStateLen * sizeof(double), s));
+    PTV_HIP(hipMemcpyAsync(wk.div.p, rhs, nbytes, hipMemcpyDeviceToDevice, s));
+    PTV_TRY(sol.div_stats(3));  // the mean of rhs over the fluid voxels, which k_rhs subtracts
+    double ms = 0.0, med = 0.0;
+    PTV_TRY(sol.solve(h_final, ms, med));
+    PTV_HIP(hipMemcpyAsync(X, wk.x.p, nbytes, hipMemcpyDeviceToDevice, s));  // solid entries are the memset's 0
+    PTV_HIP(hipStreamSynchronize(s));
+    if (res) {
+        res->n_fluid = (int64_t)h_final[S_NFLUID];
+        res->istop = (int)h_final[S_ISTOP];
+        res->itn = (int)h_final[S_ITN];
+        res->bnorm = h_final[S_BNORM];
+        res->rnorm = h_final[S_RNORM];
+        res->ms_solve = ms;
+        res->ms_iter_median = med;
+    }
+    return PTV_OK;
+}
+
 int clean_run(CleanWork &wk, const CleanGrid &g, const CleanSolve &sv, const uint8_t *M, const double *U,
               const double *V, const double *W, double *Uo, double *Vo, double *Wo, hipStream_t s,
               ptv_clean_stats *st) {

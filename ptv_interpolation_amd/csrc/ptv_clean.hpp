@@ -36,6 +36,16 @@ struct CleanSolve {
 int clean_run(CleanWork &wk, const CleanGrid &g, const CleanSolve &sv, const uint8_t *M, const double *U,
               const double *V, const double *W, double *Uo, double *Vo, double *Wo, hipStream_t s,
               ptv_clean_stats *st);
+// One LSQR solve of A x = rhs - mean(rhs over fluid) for a caller's device right-hand side
+// (solve_poisson without a Dirichlet set, physics.py:331-340): the solver of clean_run, untouched.
+// sv.iterations is not read.  X (solid voxels 0) may alias rhs.  Synchronises `s`.
+struct CleanRhsResult {
+    int64_t n_fluid;
+    int istop, itn;
+    double bnorm, rnorm, ms_solve, ms_iter_median;
+};
+int clean_solve_rhs(CleanWork &wk, const CleanGrid &g, const CleanSolve &sv, const uint8_t *M, const double *rhs,
+                    double *X, hipStream_t s, CleanRhsResult *res);
 int launch_clean_correction(const CleanGrid &g, const uint8_t *M, const double *U, const double *V, const double *W,
                             const double *phi, double *Uo, double *Vo, double *Wo, hipStream_t s);
 int launch_clean_laplacian(const CleanGrid &g, const uint8_t *M, const double *x, double *y, hipStream_t s);

@@ -14,6 +14,7 @@
 #include "ptv_kernels.hpp"
 #include "ptv_knn_big.hpp"
 #include "ptv_own.hpp"
+#include "ptv_pressure.hpp"
 #include "ptv_variational.hpp"
 
 namespace ptv {
@@ -97,7 +98,11 @@ struct ptv_ctx {
     ptv::DevBuf<double> clean_fld[4];                                 // its host calls: U, V, W (in place), phi / x
     ptv::VarWork var;                                                 // variational cleaning: CG vectors, state
     ptv::DevBuf<double> var_fld[6];                                   // its host calls: fields (in place) / x, y
-    ptv::DevBuf<double> flow_part, flow_res;                          // flow analysis: per-block partials, reduced rows
+    ptv::PressWork press;                                             // pressure recovery: stencil scratch, CG vectors
+    ptv::DevBuf<double> press_fld[7];                                 // its host calls: U, V, W | F, rhs / x
+    ptv::DevBuf<uint8_t> press_dir;                                   //   and the Dirichlet grid
+    ptv::Event ev_press[4];                                           // chain start, around the divergence, end
+    ptv::DevBuf<double> flow_part, flow_res;                        // flow analysis: per-block partials, reduced rows
     ptv::DevBuf<uint8_t> flow_fld[3], flow_out[4];                   // its host calls: inputs (U, V, W | S, O), outputs
     ptv::Event ev_flow0, ev_flow1;                                    // around its kernels
     ptv::DevBuf<double> drag_part, drag_res;                          // interface drag / gradient sums: partials, rows

@@ -1,0 +1,730 @@
+// ptv_pressure.hip — pressure recovery: force field, force divergence, anchored matrix-free CG.
+//
+// Restates velocity_analysis.compute_pressure_field (velocity_analysis.py:190-330) and the parts of
+// physics.py it calls: compute_force_divergence (:211-262) and solve_poisson's anchored branch
+// (:264-345, cg(A, b, tol=1e-10, maxiter=3000) on build_laplacian_matrix, :55-108).
+//
+// Storage as in ptv_clean.hip and ptv_variational.hip: dense float64 (nz, ny, nx) grids, x fastest,
+// a uint8 mask (nonzero = fluid); a lane owns VEC consecutive x (2 when nx is even and the buffers
+// are aligned).  Reductions are the two-stage fixed-order sums of ptv_grid_vec.hpp.
+//
+// Force field (laplacian_mask_aware, :210-269, then :273-289), three passes:
+//   k_lap     raw Laplacian of u, v, w at every voxel, lap = 0 + tz + ty + tx with
+//             t = (f_next - 2 f + f_prev) / h**2 and clamped neighbours; the voxel's code: 0 solid,
+//             1 bulk (scipy's binary_erosion: fluid with six fluid neighbours inside the domain),
+//             4 fluid not bulk; partial counts of bulk voxels
+//   k_fill    round 1 in place: a code-4 voxel averages the Laplacians of its code-1 neighbours in
+//             the order z+1, z-1, y+1, y-1, x+1, x-1 (np.roll: they wrap around the domain) and
+//             becomes code 2.  A round reads only voxels whose code is at most the round's number
+//             and writes only code-4 voxels, so it runs in place without a race
+//   k_force   round 2 fused with the force: a code-4 voxel averages its code-1 and code-2
+//             neighbours (not stored: nothing reads it later); f = mu * lap, and for rho > 0
+//             f -= rho * (u gx + v gy + w gz) with np.gradient's formula; partial sums over the
+//             fluid voxels of |fx|, |fy|, |fz|, w and 1
+// With no bulk voxel the reference returns the raw Laplacian: both fills test the device-resident
+// bulk count.
+//
+// CG: the unknowns are the fluid voxels that are not Dirichlet ("active").  x, r, p are 0 at every
+// other voxel and stay 0, so a Dirichlet neighbour enters (A p)_i = sum (p_j - p_i) h^-2 as p_j = 0
+// and counts in the diagonal: the symmetric system with the Dirichlet rows and columns eliminated.
+// One iteration (scipy _isolve/iterative.py, cg):
+//     k_pcg_scalar TOP:    rr = sum r^2;  ||r|| < rtol ||b|| stops, info 0;  else rho, beta
+//     k_pq:                p' = r + beta p (into the other p buffer),  q = A p',  partial sums of p' q
+//     k_pcg_scalar ALPHA:  alpha = rho / sum p' q
+//     k_pxr:               x += alpha p',  r -= alpha q,  partial sums of r^2
+// k_pq recomputes the six neighbours' p' from r and p with the owners' expression.  Bytes per voxel
+// and iteration: k_pq 8 r + 8 p + 8 p' + 8 q + 1 mask = 33; k_pxr 8 p' + 8 q + 8 x + 8 r reads, 8 x +
+// 8 r writes + 1 = 49; 82 in all, + 2 with a Dirichlet grid (one byte in each pass).
+// Stopping, polling and the NaN outcome are ptv_variational.hip's.
+#include <cmath>
+#include <algorithm>
+
+#include "ptv_pressure.hpp"
+#include "ptv_grid_vec.hpp"
+#include "ptv_kernels.hpp"
+
+namespace ptv {
+
+namespace {
+
+constexpr int kPoll = 8;  // CG iterations between two polls of the stop flag
+
+// device-resident state (doubles): the CG recurrence, then what the force pass leaves
+enum {
+    S_STOP = 0, S_INFO, S_ITN, S_RHO, S_RHO_PREV, S_BETA, S_ALPHA, S_RR, S_BNORM, S_THR, S_NAN, S_NDIR, S_NFLUID,
+    S_CG_COUNT,
+    F_BULK = 16, F_SFX, F_SFY, F_SFZ, F_SW, F_NFLUID, F_COUNT
+};
+constexpr int kStateLen = 24;
+static_assert(S_CG_COUNT <= F_BULK && F_COUNT <= kStateLen, "state length");
+
+enum Phase { PH_BULK = 0, PH_FORCE, PH_INIT, PH_TOP0, PH_TOP, PH_ALPHA, PH_END };
+enum Code : uint8_t { C_SOLID = 0, C_BULK = 1, C_FILL1 = 2, C_FILL2 = 3, C_OPEN = 4 };
+
+struct PArgs : GridDims {
+    double h[3];    // dx, dy, dz
+    double h2[3];   // h ** 2 (the raw Laplacian divides by it)
+    double ih2[3];  // 1.0 / h ** 2 (the matrix entries, physics.py:68)
+};
+
+struct CgCfg {
+    double rtol;
+    int maxiter;
+};
+
+struct V3 {
+    double *c[3];
+};
+struct CV3 {
+    const double *c[3];
+};
+
+// the six neighbours of voxel (x, y, z) at index i, clamped at the array ends
+struct Clamp {
+    unsigned xm, xp, ym, yp, zm, zp;
+};
+__device__ __forceinline__ Clamp clamped(const GridDims &a, unsigned i, int x, int y, int z) {
+    Clamp c;
+    c.xm = x > 0 ? i - 1 : i;
+    c.xp = x + 1 < a.nx ? i + 1 : i;
+    c.ym = y > 0 ? i - (unsigned)a.nx : i;
+    c.yp = y + 1 < a.ny ? i + (unsigned)a.nx : i;
+    c.zm = z > 0 ? i - a.plane : i;
+    c.zp = z + 1 < a.nz ? i + a.plane : i;
+    return c;
+}
+
+// raw Laplacian of three fields at every voxel, the voxel codes, partial counts of bulk voxels
+template <int VEC>
+__global__ __launch_bounds__(kGridThreads) void k_lap(PArgs a, CV3 F, const uint8_t *__restrict__ M, V3 L,
+                                                      uint8_t *__restrict__ code, double *__restrict__ part) {
+    double nbulk = 0.0;
+#pragma unroll
+    for (int it = 0; it < kGridItems; ++it) {
+        Pos p;
+        if (!group_pos<VEC>(a, it, p)) break;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+            const unsigned i = p.i + e;
+            const int x = p.x + e;
+            const Clamp c = clamped(a, i, x, p.y, p.z);
+            const bool inside = x > 0 && x + 1 < a.nx && p.y > 0 && p.y + 1 < a.ny && p.z > 0 && p.z + 1 < a.nz;
+            const bool fluid = M[i] != 0;
+            const bool bulk = fluid && inside && M[c.xm] && M[c.xp] && M[c.ym] && M[c.yp] && M[c.zm] && M[c.zp];
+            code[i] = !fluid ? C_SOLID : bulk ? C_BULK : C_OPEN;
+            nbulk += bulk ? 1.0 : 0.0;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const double *__restrict__ f = F.c[k];
+                const double fc = f[i];
+                double lap = 0.0;
+                lap += ((f[c.zp] - 2 * fc) + f[c.zm]) / a.h2[2];
+                lap += ((f[c.yp] - 2 * fc) + f[c.ym]) / a.h2[1];
+                lap += ((f[c.xp] - 2 * fc) + f[c.xm]) / a.h2[0];
+                L.c[k][i] = lap;
+            }
+        }
+    }
+    nbulk = block_sum(nbulk);
+    if (threadIdx.x == 0) part[blockIdx.x] = nbulk;
+}
+
+// the six neighbours under np.roll: they wrap around the domain; order z+1, z-1, y+1, y-1, x+1, x-1
+struct Wrap {
+    unsigned j[6];
+};
+__device__ __forceinline__ Wrap wrapped(const GridDims &a, unsigned i, int x, int y, int z) {
+    Wrap w;
+    w.j[0] = z + 1 < a.nz ? i + a.plane : i - (unsigned)z * a.plane;
+    w.j[1] = z > 0 ? i - a.plane : i + (unsigned)(a.nz - 1) * a.plane;
+    w.j[2] = y + 1 < a.ny ? i + (unsigned)a.nx : i - (unsigned)y * (unsigned)a.nx;
+    w.j[3] = y > 0 ? i - (unsigned)a.nx : i + (unsigned)(a.ny - 1) * (unsigned)a.nx;
+    w.j[4] = x + 1 < a.nx ? i + 1 : i - (unsigned)x;
+    w.j[5] = x > 0 ? i - 1 : i + (unsigned)(a.nx - 1);
+    return w;
+}
+
+// one fill round at a code-4 voxel: sum / count over the neighbours whose code is in [1, top]
+// (:252-264); false when no neighbour qualifies
+__device__ __forceinline__ bool fill_average(const Wrap &w, const uint8_t *__restrict__ code, uint8_t top, CV3 L,
+                                             double out[3]) {
+    double sum[3] = {0.0, 0.0, 0.0}, count = 0.0;
+#pragma unroll
+    for (int n = 0; n < 6; ++n) {
+        const uint8_t cn = code[w.j[n]];
+        if (cn >= C_BULK && cn <= top) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) sum[k] += L.c[k][w.j[n]];
+            count += 1.0;
+        }
+    }
+    if (count == 0.0) return false;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) out[k] = sum[k] / count;
+    return true;
+}
+
+// fill round 1, in place (see the head of the file for why that is no race)
+template <int VEC>
+__global__ __launch_bounds__(kGridThreads) void k_fill(PArgs a, const double *__restrict__ st, V3 L,
+                                                       uint8_t *code) {
+    if (st[F_BULK] == 0.0) return;
+#pragma unroll
+    for (int it = 0; it < kGridItems; ++it) {
+        Pos p;
+        if (!group_pos<VEC>(a, it, p)) break;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+            const unsigned i = p.i + e;
+            if (code[i] != C_OPEN) continue;
+            double v[3];
+            if (!fill_average(wrapped(a, i, p.x + e, p.y, p.z), code, C_BULK, CV3{{L.c[0], L.c[1], L.c[2]}}, v))
+                continue;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) L.c[k][i] = v[k];
+            code[i] = C_FILL1;
+        }
+    }
+}
+
+// np.gradient along one axis at position t of n (n >= 2) with the neighbours' values
+__device__ __forceinline__ double grad1(double fm, double fc, double fp, int t, int n, double h) {
+    if (t == 0) return (fp - fc) / h;
+    if (t == n - 1) return (fc - fm) / h;
+    return (fp - fm) / (2. * h);
+}
+
+// fill round 2 fused with the force field and its sums
+template <int VEC>
+__global__ __launch_bounds__(kGridThreads) void k_force(PArgs a, const double *__restrict__ st, double mu, double rho,
+                                                        CV3 F, const uint8_t *__restrict__ M, CV3 L,
+                                                        const uint8_t *__restrict__ code, V3 O,
+                                                        double *__restrict__ part, unsigned npart) {
+    const bool fill = st[F_BULK] != 0.0;
+    double s[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int it = 0; it < kGridItems; ++it) {
+        Pos p;
+        if (!group_pos<VEC>(a, it, p)) break;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+            const unsigned i = p.i + e;
+            const int x = p.x + e;
+            double lap[3] = {L.c[0][i], L.c[1][i], L.c[2][i]};
+            if (fill && code[i] == C_OPEN) (void)fill_average(wrapped(a, i, x, p.y, p.z), code, C_FILL1, L, lap);
+            double f[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) f[k] = mu * lap[k];
+            const double vel[3] = {F.c[0][i], F.c[1][i], F.c[2][i]};
+            if (rho > 0.0) {
+                const Clamp c = clamped(a, i, x, p.y, p.z);
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    const double *__restrict__ g = F.c[k];
+                    const double gx = grad1(g[c.xm], vel[k], g[c.xp], x, a.nx, a.h[0]);
+                    const double gy = grad1(g[c.ym], vel[k], g[c.yp], p.y, a.ny, a.h[1]);
+                    const double gz = grad1(g[c.zm], vel[k], g[c.zp], p.z, a.nz, a.h[2]);
+                    const double adv = (vel[0] * gx + vel[1] * gy) + vel[2] * gz;
+                    f[k] = f[k] - rho * adv;
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 3; ++k) O.c[k][i] = f[k];
+            if (M[i]) {
+                s[0] += fabs(f[0]);
+                s[1] += fabs(f[1]);
+                s[2] += fabs(f[2]);
+                s[3] += vel[2];
+                s[4] += 1.0;
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        const double r = block_sum(s[k]);
+        if (threadIdx.x == 0) part[k * npart + blockIdx.x] = r;
+    }
+}
+
+// the face value between a voxel and its next one along an axis (physics.py:227-244)
+__device__ __forceinline__ double face(double fc, double fn, bool mc, bool mn, bool inhom) {
+    if (mc && mn) return 0.5 * (fc + fn);
+    if (inhom && mc) return fc;
+    if (inhom && mn) return fn;
+    return 0.0;
+}
+// (face_i - face_{i-1}) / h at position t of n; the faces outside the array are 0
+__device__ __forceinline__ double flux_term(const double *__restrict__ f, const uint8_t *__restrict__ M, unsigned i,
+                                            unsigned stride, int t, int n, double h, bool inhom) {
+    const double fc = f[i];
+    const bool mc = M[i] != 0;
+    const double hi = t + 1 < n ? face(fc, f[i + stride], mc, M[i + stride] != 0, inhom) : 0.0;
+    const double lo = t > 0 ? face(f[i - stride], fc, M[i - stride] != 0, mc, inhom) : 0.0;
+    return (hi - lo) / h;
+}
+
+// force divergence at every voxel (physics.py:211-262): x term + y term + z term
+template <int VEC>
+__global__ __launch_bounds__(kGridThreads) void k_fdiv(PArgs a, int inhom, CV3 F, const uint8_t *__restrict__ M,
+                                                       double *__restrict__ D) {
+#pragma unroll
+    for (int it = 0; it < kGridItems; ++it) {
+        Pos p;
+        if (!group_pos<VEC>(a, it, p)) break;
+        DV<VEC> d;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+            const unsigned i = p.i + e;
+            const double tx = flux_term(F.c[0], M, i, 1u, p.x + e, a.nx, a.h[0], inhom != 0);
+            const double ty = flux_term(F.c[1], M, i, (unsigned)a.nx, p.y, a.ny, a.h[1], inhom != 0);
+            const double tz = flux_term(F.c[2], M, i, a.plane, p.z, a.nz, a.h[2], inhom != 0);
+            d.e[e] = (tx + ty) + tz;
+        }
+        std_<VEC>(D + p.i, d);
+    }
+}
+
+// Dir = the fluid voxels of plane z
+__global__ __launch_bounds__(kGridThreads) void k_anchor(GridDims a, unsigned z, const uint8_t *__restrict__ M,
+                                                         uint8_t *__restrict__ Dir) {
+    const unsigned i = blockIdx.x * kGridThreads + threadIdx.x;
+    if (i >= a.n) return;
+    Dir[i] = (i / a.plane == z && M[i]) ? 1 : 0;
+}
+
+template <int VEC>
+__device__ __forceinline__ MV<VEC> active_of(const uint8_t *__restrict__ M, const uint8_t *__restrict__ Dir,
+                                             unsigned i) {
+    MV<VEC> m = ldmk<VEC>(M + i);
+    if (Dir) {
+        const MV<VEC> d = ldmk<VEC>(Dir + i);
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) m.e[e] = (m.e[e] && !d.e[e]) ? 1 : 0;
+    }
+    return m;
+}
+
+// x = 0, r = b at active voxels (0 elsewhere); partial sums of b^2, Dirichlet and fluid counts
+template <int VEC>
+__global__ __launch_bounds__(kGridThreads) void k_pinit(PArgs a, const double *__restrict__ B,
+                                                        const uint8_t *__restrict__ M,
+                                                        const uint8_t *__restrict__ Dir, double *__restrict__ X,
+                                                        double *__restrict__ R, double *__restrict__ part,
+                                                        unsigned npart) {
+    double ss = 0.0, nd = 0.0, nf = 0.0;
+#pragma unroll
+    for (int it = 0; it < kGridItems; ++it) {
+        Pos p;
+        if (!group_pos<VEC>(a, it, p)) break;
+        const MV<VEC> mc = ldmk<VEC>(M + p.i), act = active_of<VEC>(M, Dir, p.i);
+        DV<VEC> b = ldd<VEC>(B + p.i), z;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+            z.e[e] = 0.0;
+            b.e[e] = act.e[e] ? b.e[e] : 0.0;
+            ss += b.e[e] * b.e[e];
+            nf += mc.e[e] ? 1.0 : 0.0;
+            nd += (mc.e[e] && !act.e[e]) ? 1.0 : 0.0;
+        }
+        std_<VEC>(R + p.i, b);
+        std_<VEC>(X + p.i, z);
+    }
+    ss = block_sum(ss);
+    nd = block_sum(nd);
+    nf = block_sum(nf);
+    if (threadIdx.x == 0) {
+        part[blockIdx.x] = ss;
+        part[npart + blockIdx.x] = nd;
+        part[2 * npart + blockIdx.x] = nf;
+    }
+}
+
+// p' = r + beta p on active voxels (into Pn), q = A p', partial sums of p' q.  Neighbour offsets are
+// clamped at the domain faces, so every load is in bounds and unconditional; a face or solid
+// neighbour's term is dropped.  Term order: x-, x+, y-, y+, z-, z+ (physics.py:76-77).
+template <int VEC>
+__global__ __launch_bounds__(kGridThreads) void k_pq(PArgs a, const double *__restrict__ st,
+                                                     const double *__restrict__ R, const double *__restrict__ P,
+                                                     double *__restrict__ Pn, double *__restrict__ Q,
+                                                     const uint8_t *__restrict__ M, const uint8_t *__restrict__ Dir,
+                                                     double *__restrict__ part) {
+    if (st[S_STOP] != 0.0) return;
+    const double beta = st[S_BETA];
+    double ss = 0.0;
+#pragma unroll
+    for (int it = 0; it < kGridItems; ++it) {
+        Pos p;
+        if (!group_pos<VEC>(a, it, p)) break;
+        const unsigned i = p.i;
+        const MV<VEC> act = active_of<VEC>(M, Dir, i);
+        bool any = false;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) any = any || act.e[e];
+        if (!any) continue;
+        const bool xl = p.x > 0, xh = p.x + VEC < a.nx, yl = p.y > 0, yh = p.y + 1 < a.ny, zl = p.z > 0,
+                   zh = p.z + 1 < a.nz;
+        const unsigned il = i - (xl ? 1u : 0u), ir = i + VEC - 1 + (xh ? 1u : 0u);
+        const unsigned oym = yl ? (unsigned)a.nx : 0u, oyp = yh ? (unsigned)a.nx : 0u;
+        const unsigned ozm = zl ? a.plane : 0u, ozp = zh ? a.plane : 0u;
+        const MV<VEC> mc = ldmk<VEC>(M + i);
+        const uint8_t ml = M[il], mr = M[ir];
+        const MV<VEC> mym = ldmk<VEC>(M + i - oym), myp = ldmk<VEC>(M + i + oyp);
+        const MV<VEC> mzm = ldmk<VEC>(M + i - ozm), mzp = ldmk<VEC>(M + i + ozp);
+        const DV<VEC> rc = ldd<VEC>(R + i), pc = ldd<VEC>(P + i);
+        const double cl = R[il] + beta * P[il], cr = R[ir] + beta * P[ir];
+        DV<VEC> ym = ldd<VEC>(R + i - oym), yp = ldd<VEC>(R + i + oyp);
+        DV<VEC> zm = ldd<VEC>(R + i - ozm), zp = ldd<VEC>(R + i + ozp);
+        const DV<VEC> pym = ldd<VEC>(P + i - oym), pyp = ldd<VEC>(P + i + oyp);
+        const DV<VEC> pzm = ldd<VEC>(P + i - ozm), pzp = ldd<VEC>(P + i + ozp);
+        DV<VEC> c, q;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+            // an inactive voxel's r and p are 0, so the owners' expression gives the neighbours 0 too
+            c.e[e] = act.e[e] ? rc.e[e] + beta * pc.e[e] : 0.0;
+            ym.e[e] = ym.e[e] + beta * pym.e[e];
+            yp.e[e] = yp.e[e] + beta * pyp.e[e];
+            zm.e[e] = zm.e[e] + beta * pzm.e[e];
+            zp.e[e] = zp.e[e] + beta * pzp.e[e];
+        }
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+            const double xi = c.e[e];
+            const bool hasl = e > 0 ? true : xl, hasr = e + 1 < VEC ? true : xh;
+            const double vl = e > 0 ? c.e[e > 0 ? e - 1 : 0] : cl;
+            const double vr = e + 1 < VEC ? c.e[e + 1 < VEC ? e + 1 : e] : cr;
+            const bool fl = (e > 0 ? mc.e[e > 0 ? e - 1 : 0] : ml) != 0;
+            const bool fr = (e + 1 < VEC ? mc.e[e + 1 < VEC ? e + 1 : e] : mr) != 0;
+            double acc = 0.0;
+            if (hasl && fl) acc += (vl - xi) * a.ih2[0];
+            if (hasr && fr) acc += (vr - xi) * a.ih2[0];
+            if (yl && mym.e[e]) acc += (ym.e[e] - xi) * a.ih2[1];
+            if (yh && myp.e[e]) acc += (yp.e[e] - xi) * a.ih2[1];
+            if (zl && mzm.e[e]) acc += (zm.e[e] - xi) * a.ih2[2];
+            if (zh && mzp.e[e]) acc += (zp.e[e] - xi) * a.ih2[2];
+            q.e[e] = act.e[e] ? acc : 0.0;
+            if (act.e[e]) ss += xi * acc;
+        }
+        std_<VEC>(Pn + i, c);
+        std_<VEC>(Q + i, q);
+    }
+    ss = block_sum(ss);
+    if (threadIdx.x == 0) part[blockIdx.x] = ss;
+}
+
+// x += alpha p;  r -= alpha q;  partial sums of the new r^2
+template <int VEC>
+__global__ __launch_bounds__(kGridThreads) void k_pxr(PArgs a, const double *__restrict__ st,
+                                                      const double *__restrict__ P, const double *__restrict__ Q,
+                                                      double *__restrict__ X, double *__restrict__ R,
+                                                      const uint8_t *__restrict__ M, const uint8_t *__restrict__ Dir,
+                                                      double *__restrict__ part) {
+    if (st[S_STOP] != 0.0) return;
+    const double alpha = st[S_ALPHA];
+    double ss = 0.0;
+#pragma unroll
+    for (int it = 0; it < kGridItems; ++it) {
+        Pos p;
+        if (!group_pos<VEC>(a, it, p)) break;
+        const unsigned i = p.i;
+        const MV<VEC> act = active_of<VEC>(M, Dir, i);
+        bool any = false;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) any = any || act.e[e];
+        if (!any) continue;
+        const DV<VEC> pc = ldd<VEC>(P + i), qc = ldd<VEC>(Q + i);
+        DV<VEC> x = ldd<VEC>(X + i), r = ldd<VEC>(R + i);
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+            if (!act.e[e]) continue;
+            x.e[e] = x.e[e] + alpha * pc.e[e];
+            r.e[e] = r.e[e] - alpha * qc.e[e];
+            ss += r.e[e] * r.e[e];
+        }
+        std_<VEC>(X + i, x);
+        std_<VEC>(R + i, r);
+    }
+    ss = block_sum(ss);
+    if (threadIdx.x == 0) part[blockIdx.x] = ss;
+}
+
+// the output: x at active voxels, 0 at solid and Dirichlet voxels; NaN at every fluid voxel when the
+// right-hand side held one (scipy's x += alpha p with alpha = NaN reaches the Dirichlet entries too)
+template <int VEC>
+__global__ __launch_bounds__(kGridThreads) void k_pout(PArgs a, const double *__restrict__ st,
+                                                       const double *__restrict__ X, const uint8_t *__restrict__ M,
+                                                       const uint8_t *__restrict__ Dir, double *__restrict__ O) {
+    const bool nan = st[S_NAN] != 0.0;
+    const double qnan = __longlong_as_double(0x7ff8000000000000LL);
+#pragma unroll
+    for (int it = 0; it < kGridItems; ++it) {
+        Pos p;
+        if (!group_pos<VEC>(a, it, p)) break;
+        const MV<VEC> mc = ldmk<VEC>(M + p.i), act = active_of<VEC>(M, Dir, p.i);
+        DV<VEC> x = ldd<VEC>(X + p.i);
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) x.e[e] = !mc.e[e] ? 0.0 : nan ? qnan : act.e[e] ? x.e[e] : 0.0;
+        std_<VEC>(O + p.i, x);
+    }
+}
+
+// Second reduction stage and the scalar steps.  One block sums the partials in a fixed order, then
+// thread 0 alone advances the state as scipy's cg does between its vector operations.
+__global__ __launch_bounds__(kGridFinalThreads) void k_pcg_scalar(int phase, CgCfg cfg, double *__restrict__ st,
+                                                                   const double *__restrict__ part, unsigned npart) {
+    const bool solver = phase == PH_TOP0 || phase == PH_TOP || phase == PH_ALPHA || phase == PH_END;
+    if (solver && st[S_STOP] != 0.0) return;
+    double r[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    const int rows = phase == PH_FORCE ? 5 : phase == PH_INIT ? 3 : phase == PH_TOP0 ? 0 : 1;
+    for (int k = 0; k < rows; ++k) r[k] = partial_sum(part + k * npart, npart);
+    if (threadIdx.x != 0) return;
+    const double r0 = r[0];
+    switch (phase) {
+    case PH_BULK:
+        st[F_BULK] = r0;
+        break;
+    case PH_FORCE:
+        st[F_SFX] = r[0];
+        st[F_SFY] = r[1];
+        st[F_SFZ] = r[2];
+        st[F_SW] = r[3];
+        st[F_NFLUID] = r[4];
+        break;
+    case PH_INIT: {  // bnrm2, the threshold max(atol, rtol * bnrm2) with atol = 0, the early returns
+        const double bnorm = sqrt(r0);
+        for (int k = 0; k < S_CG_COUNT; ++k) st[k] = 0.0;
+        st[S_NDIR] = r[1];
+        st[S_NFLUID] = r[2];
+        st[S_RR] = r0;
+        st[S_BNORM] = bnorm;
+        st[S_THR] = cfg.rtol * bnorm > 0.0 ? cfg.rtol * bnorm : 0.0;
+        if (bnorm == 0.0 || cfg.maxiter <= 0) {
+            st[S_STOP] = 1.0;  // zeros, info = 0
+        } else if (r0 != r0) {  // a NaN in b: alpha is NaN in the first step and x is NaN from then on
+            st[S_NAN] = 1.0;
+            st[S_INFO] = (double)cfg.maxiter;
+            st[S_ITN] = (double)cfg.maxiter;
+            st[S_STOP] = 1.0;
+        }
+        break;
+    }
+    case PH_TOP0:
+    case PH_TOP: {  // the top of an iteration: the only convergence test, then rho and beta
+        const double rr = phase == PH_TOP0 ? st[S_RR] : r0;
+        st[S_RR] = rr;
+        if (sqrt(rr) < st[S_THR]) {
+            st[S_STOP] = 1.0;  // info = 0
+            break;
+        }
+        st[S_RHO] = rr;
+        st[S_BETA] = phase == PH_TOP0 ? 0.0 : rr / st[S_RHO_PREV];
+        break;
+    }
+    case PH_ALPHA:
+        st[S_ALPHA] = st[S_RHO] / r0;
+        st[S_RHO_PREV] = st[S_RHO];
+        st[S_ITN] += 1.0;  // this iteration's updates follow unconditionally
+        break;
+    case PH_END:  // the loop ran out: no test after the last step
+        st[S_RR] = r0;
+        st[S_INFO] = (double)cfg.maxiter;
+        st[S_STOP] = 1.0;
+        break;
+    default:
+        break;
+    }
+}
+
+int make_args(const PressGrid &g, PArgs &a) {
+    if (g.nx <= 0 || g.ny <= 0 || g.nz <= 0) {
+        set_error("pressure: dimensions must be positive");
+        return PTV_E_ARG;
+    }
+    const long long n = (long long)g.nx * g.ny * g.nz;
+    if (n > 0x7fff0000LL) {
+        set_error("pressure: grids of 2^31 voxels or more are not supported");
+        return PTV_E_ARG;
+    }
+    if (!(g.dx > 0.0) || !(g.dy > 0.0) || !(g.dz > 0.0) || !std::isfinite(g.dx) || !std::isfinite(g.dy) ||
+        !std::isfinite(g.dz)) {
+        set_error("pressure: spacings must be positive finite numbers");
+        return PTV_E_ARG;
+    }
+    a.nx = g.nx;
+    a.ny = g.ny;
+    a.nz = g.nz;
+    a.n = (unsigned)n;
+    a.plane = (unsigned)g.nx * (unsigned)g.ny;
+    const double h[3] = {g.dx, g.dy, g.dz};
+    for (int k = 0; k < 3; ++k) {
+        a.h[k] = h[k];
+        a.h2[k] = h[k] * h[k];
+        a.ih2[k] = 1.0 / (h[k] * h[k]);
+    }
+    return PTV_OK;
+}
+
+#define PRESS_LAUNCH(kernel, vec2, nb, s, ...)                                                            \
+    do {                                                                                                  \
+        if (vec2) hipLaunchKernelGGL(kernel<2>, dim3(nb), dim3(kGridThreads), 0, s, __VA_ARGS__);          \
+        else hipLaunchKernelGGL(kernel<1>, dim3(nb), dim3(kGridThreads), 0, s, __VA_ARGS__);               \
+        PTV_HIP(hipGetLastError());                                                                       \
+    } while (0)
+
+int scalar(PressWork &wk, int phase, const CgCfg &cfg, unsigned nb, hipStream_t s) {
+    hipLaunchKernelGGL(k_pcg_scalar, dim3(1), dim3(kGridFinalThreads), 0, s, phase, cfg, wk.state.p, wk.part.p, nb);
+    PTV_HIP(hipGetLastError());
+    return PTV_OK;
+}
+
+int event(PressWork &wk, size_t k, hipStream_t s) {
+    if (wk.ev.size() <= k) wk.ev.resize(k + 1);
+    return wk.ev[k].record(s);
+}
+
+}  // namespace
+
+int press_force(PressWork &wk, const PressGrid &g, double mu, double rho, const uint8_t *M, const double *U,
+                const double *V, const double *W, double *Fx, double *Fy, double *Fz, hipStream_t s,
+                ptv_pressure_stats *st) {
+    PArgs a{};
+    PTV_TRY(make_args(g, a));
+    if (!std::isfinite(mu) || !std::isfinite(rho)) {
+        set_error("pressure: mu and rho must be finite");
+        return PTV_E_ARG;
+    }
+    if (rho > 0.0 && (a.nx < 2 || a.ny < 2 || a.nz < 2)) {
+        set_error("pressure: rho > 0 needs at least 2 voxels along every axis (np.gradient)");
+        return PTV_E_ARG;
+    }
+    const size_t n = a.n;
+    // the stencil passes address single elements: one x per lane serves every alignment
+    const unsigned nb = blocks_for(a.n, 1);
+    PTV_TRY(wk.lap.ensure(3 * n));
+    PTV_TRY(wk.code.ensure(n));
+    PTV_TRY(wk.part.ensure(5 * (size_t)nb));
+    PTV_TRY(wk.state.ensure(kStateLen));
+    PTV_TRY(wk.h_state.ensure(3 * kStateLen));
+    double *h_final = wk.h_state.p + 2 * kStateLen;
+    const CgCfg cfg{0.0, 0};
+    const V3 L{{wk.lap.p, wk.lap.p + n, wk.lap.p + 2 * n}};
+    const CV3 cL{{L.c[0], L.c[1], L.c[2]}}, F{{U, V, W}};
+    PTV_TRY(event(wk, 0, s));
+    hipLaunchKernelGGL(k_lap<1>, dim3(nb), dim3(kGridThreads), 0, s, a, F, M, L, wk.code.p, wk.part.p);
+    PTV_HIP(hipGetLastError());
+    PTV_TRY(scalar(wk, PH_BULK, cfg, nb, s));
+    hipLaunchKernelGGL(k_fill<1>, dim3(nb), dim3(kGridThreads), 0, s, a, (const double *)wk.state.p, L, wk.code.p);
+    PTV_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_force<1>, dim3(nb), dim3(kGridThreads), 0, s, a, (const double *)wk.state.p, mu, rho, F, M,
+                       cL, (const uint8_t *)wk.code.p, V3{{Fx, Fy, Fz}}, wk.part.p, nb);
+    PTV_HIP(hipGetLastError());
+    PTV_TRY(scalar(wk, PH_FORCE, cfg, nb, s));
+    PTV_HIP(hipMemcpyAsync(h_final, wk.state.p, kStateLen * sizeof(double), hipMemcpyDeviceToHost, s));
+    PTV_TRY(event(wk, 1, s));
+    PTV_HIP(hipStreamSynchronize(s));
+    if (st) {
+        st->n_fluid = (int64_t)h_final[F_NFLUID];
+        st->sum_abs_fx = h_final[F_SFX];
+        st->sum_abs_fy = h_final[F_SFY];
+        st->sum_abs_fz = h_final[F_SFZ];
+        st->sum_w = h_final[F_SW];
+        float ms = 0.f;
+        PTV_HIP(hipEventElapsedTime(&ms, wk.ev[0], wk.ev[1]));
+        st->ms_force = ms;
+    }
+    return PTV_OK;
+}
+
+int press_divergence(const PressGrid &g, bool inhomogeneous, const uint8_t *M, const double *Fx, const double *Fy,
+                     const double *Fz, double *D, hipStream_t s) {
+    PArgs a{};
+    PTV_TRY(make_args(g, a));
+    const bool vec2 = a.nx % 2 == 0 && all_aligned16(D);
+    const unsigned nb = blocks_for(a.n, vec2 ? 2 : 1);
+    PRESS_LAUNCH(k_fdiv, vec2, nb, s, a, inhomogeneous ? 1 : 0, CV3{{Fx, Fy, Fz}}, M, D);
+    return PTV_OK;
+}
+
+int press_anchor_plane(const PressGrid &g, int z, const uint8_t *M, uint8_t *Dir, hipStream_t s) {
+    PArgs a{};
+    PTV_TRY(make_args(g, a));
+    if (z < 0 || z >= a.nz) {
+        set_error("pressure: the anchor plane lies outside the grid");
+        return PTV_E_ARG;
+    }
+    const unsigned nb = (a.n + kGridThreads - 1) / kGridThreads;
+    hipLaunchKernelGGL(k_anchor, dim3(nb), dim3(kGridThreads), 0, s, (GridDims)a, (unsigned)z, M, Dir);
+    PTV_HIP(hipGetLastError());
+    return PTV_OK;
+}
+
+int press_cg(PressWork &wk, const PressGrid &g, double rtol, int maxiter, const uint8_t *M, const uint8_t *Dir,
+             const double *B, double *X, hipStream_t s, ptv_pressure_stats *st) {
+    PArgs a{};
+    PTV_TRY(make_args(g, a));
+    if (!std::isfinite(rtol) || maxiter < 0) {
+        set_error("pressure: rtol must be finite and maxiter non-negative");
+        return PTV_E_ARG;
+    }
+    const size_t n = a.n, nbytes = n * sizeof(double);
+    const bool vec2 = a.nx % 2 == 0 && all_aligned16(B, X) && aligned(M, 2) && (!Dir || aligned(Dir, 2));
+    const unsigned nb = blocks_for(a.n, vec2 ? 2 : 1);
+    for (DevBuf<double> *b : {&wk.x, &wk.r, &wk.p[0], &wk.p[1], &wk.q}) PTV_TRY(b->ensure(n));
+    PTV_TRY(wk.part.ensure(5 * (size_t)blocks_for(a.n, 1)));
+    PTV_TRY(wk.state.ensure(kStateLen));
+    PTV_TRY(wk.h_state.ensure(3 * kStateLen));
+    double *h_final = wk.h_state.p + 2 * kStateLen;
+    const size_t sbytes = kStateLen * sizeof(double);
+    const CgCfg cfg{rtol, maxiter};
+    const double *cst = wk.state.p;
+
+    PTV_TRY(event(wk, 2, s));
+    PTV_HIP(hipMemsetAsync(wk.p[0].p, 0, nbytes, s));
+    PTV_HIP(hipMemsetAsync(wk.p[1].p, 0, nbytes, s));
+    PTV_HIP(hipMemsetAsync(wk.q.p, 0, nbytes, s));
+    PRESS_LAUNCH(k_pinit, vec2, nb, s, a, B, M, Dir, wk.x.p, wk.r.p, wk.part.p, nb);
+    PTV_TRY(scalar(wk, PH_INIT, cfg, nb, s));
+    PTV_TRY(event(wk, 3, s));
+    int batches = 0, cur = 0;  // p[cur] holds the last direction
+    bool stopped = false;
+    std::vector<int> batch_iters;
+    for (int done = 0; done < maxiter && !stopped; done += kPoll, ++batches) {
+        const int cnt = std::min(kPoll, maxiter - done);
+        for (int k = 0; k < cnt; ++k) {
+            PTV_TRY(scalar(wk, done + k == 0 ? PH_TOP0 : PH_TOP, cfg, nb, s));
+            PRESS_LAUNCH(k_pq, vec2, nb, s, a, cst, (const double *)wk.r.p, (const double *)wk.p[cur].p,
+                         wk.p[cur ^ 1].p, wk.q.p, M, Dir, wk.part.p);
+            cur ^= 1;
+            PTV_TRY(scalar(wk, PH_ALPHA, cfg, nb, s));
+            PRESS_LAUNCH(k_pxr, vec2, nb, s, a, cst, (const double *)wk.p[cur].p, (const double *)wk.q.p, wk.x.p,
+                         wk.r.p, M, Dir, wk.part.p);
+        }
+        batch_iters.push_back(cnt);
+        PTV_HIP(hipMemcpyAsync(wk.h_state.p + (batches & 1) * kStateLen, wk.state.p, sbytes, hipMemcpyDeviceToHost, s));
+        PTV_TRY(event(wk, 4 + batches, s));
+        if (batches >= 1) {  // poll one batch behind the enqueue: the device never waits for the host
+            PTV_HIP(hipEventSynchronize(wk.ev[4 + batches - 1]));
+            stopped = wk.h_state.p[((batches - 1) & 1) * kStateLen + S_STOP] != 0.0;
+        }
+    }
+    PTV_TRY(scalar(wk, PH_END, cfg, nb, s));
+    PTV_TRY(event(wk, 4 + batches, s));
+    PRESS_LAUNCH(k_pout, vec2, nb, s, a, cst, (const double *)wk.x.p, M, Dir, X);
+    PTV_HIP(hipMemcpyAsync(h_final, wk.state.p, sbytes, hipMemcpyDeviceToHost, s));
+    PTV_HIP(hipStreamSynchronize(s));
+    if (st) {
+        st->solver = 0;
+        st->itn = (int32_t)h_final[S_ITN];
+        st->info = (int32_t)h_final[S_INFO];
+        st->bnorm = h_final[S_BNORM];
+        st->rnorm = sqrt(h_final[S_RR]);
+        st->n_fluid = (int64_t)h_final[S_NFLUID];
+        st->n_dirichlet = (int64_t)h_final[S_NDIR];
+        float ms = 0.f;
+        PTV_HIP(hipEventElapsedTime(&ms, wk.ev[2], wk.ev[4 + batches]));
+        st->ms_solve = ms;
+        PTV_TRY(median_iter_ms(wk.ev, 3, batch_iters, st->itn, st->ms_solve, st->ms_iter_median));
+    }
+    return PTV_OK;
+}
+
+}  // namespace ptv

@@ -22,7 +22,10 @@ which the reference's call still uses.  The package's own ``clean_divergence`` d
 refusing ``method='variational'``; call ``clean_divergence_variational`` directly, or opt in through
 the repo-root shim (``PTV_GPU_CLEAN_VARIATIONAL=1``).
 
-``solve_poisson`` (physics.py:264-345) stays with the reference.
+``compute_force_divergence`` (physics.py:211-262) and ``solve_poisson`` (:264-345) run on the GPU
+too (csrc/ptv_pressure.hip): the divergence bit-identical, the solve by matrix-free
+CG on the symmetric system with the Dirichlet rows and columns eliminated (zero Dirichlet values
+only), or by the LSQR above when there is no Dirichlet set.
 """
 from __future__ import annotations
 
@@ -31,7 +34,7 @@ import numpy as np
 from . import _lib, launcher
 
 __all__ = ["compute_consistent_divergence", "apply_consistent_correction", "clean_divergence_projection",
-           "clean_divergence_variational", "clean_divergence"]
+           "clean_divergence_variational", "clean_divergence", "compute_force_divergence", "solve_poisson"]
 
 
 def _result_dtype(ft, h):
@@ -173,3 +176,65 @@ def clean_divergence(u, v, w, mask, dx, dy, dz, iterations=3, method='projection
         raise NotImplementedError("method='variational' is not on the GPU path (use the reference's "
                                   "clean_divergence_variational)")
     return clean_divergence_projection(u, v, w, mask, dx, dy, dz, iterations=iterations)
+
+
+# ---- force divergence and Poisson solve (physics.py:211-345) ----
+def _grid_args(arrays, mask, dx, dy, dz, what):
+    if mask is None:
+        raise ValueError("mask is required (True = fluid)")
+    mask = np.asarray(mask)
+    arrays = [np.asarray(a) for a in arrays]
+    if any(a.shape != mask.shape for a in arrays) or mask.ndim != 3:
+        raise ValueError(f"{what} and mask must share one 3-D shape, got {[a.shape for a in arrays]}, {mask.shape}")
+    for a in arrays:
+        if a.dtype != np.float64:
+            raise NotImplementedError(f"field dtype {a.dtype} (GPU pressure path: float64)")
+    if mask.dtype != np.bool_:
+        raise NotImplementedError(f"mask dtype {mask.dtype} (GPU pressure path: bool, True = fluid)")
+    for h in (dx, dy, dz):
+        if np.ndim(h) != 0 or not (np.isfinite(h) and h > 0):
+            raise ValueError(f"spacings must be positive finite scalars, got {h!r}")
+    return arrays, mask
+
+
+def _wall_bc_arg(wall_bc):
+    if wall_bc not in _lib.WALL_BC:
+        raise ValueError(f"unknown wall_bc {wall_bc!r} (one of {sorted(_lib.WALL_BC)})")
+
+
+def compute_force_divergence(fx, fy, fz, mask, dx, dy, dz, wall_bc='zero-neumann'):
+    """physics.py:211-262 on the GPU: the face-flux divergence of a force field at every voxel
+    (under 'inhomogeneous' solid voxels next to fluid get non-zero values, as in the reference).
+    Bit-identical to the reference."""
+    (fx, fy, fz), mask = _grid_args((fx, fy, fz), mask, dx, dy, dz, "fx, fy, fz")
+    _wall_bc_arg(wall_bc)
+    if mask.size == 0:
+        return np.zeros(mask.shape)
+    return _ctx().force_divergence(fx, fy, fz, mask, float(dx), float(dy), float(dz), wall_bc)
+
+
+def solve_poisson(source, mask, dx, dy, dz, force_field=None, wall_bc='inhomogeneous', dirichlet_mask=None, dirichlet_values=None):
+    """physics.py:264-345 on the GPU: Lap(p) = source (or the divergence of ``force_field``) on the
+    fluid voxels.  With a ``dirichlet_mask`` the solve is scipy's ``cg(A, b, tol=1e-10,
+    maxiter=3000)``, matrix-free; without one, ``lsqr`` on ``b - mean(b)`` with the reference's
+    settings.  Only zero Dirichlet values are supported: for other values the reference subtracts
+    the Dirichlet column from ``b`` and also keeps it in the matrix, which counts it twice."""
+    src = (source,) if force_field is None else tuple(force_field)
+    if force_field is None and source is None:
+        raise ValueError("either source or force_field is required")
+    src, mask = _grid_args(src, mask, dx, dy, dz, "the right-hand side")
+    _wall_bc_arg(wall_bc)
+    dm = None
+    if dirichlet_mask is not None:
+        dm = np.asarray(dirichlet_mask)
+        if dm.shape != mask.shape or dm.dtype != np.bool_:
+            raise ValueError(f"dirichlet_mask must be a bool array of shape {mask.shape}")
+        if dirichlet_values is not None and np.any(np.asarray(dirichlet_values) != 0):
+            raise ValueError("non-zero dirichlet_values are not supported: the reference subtracts the Dirichlet "
+                             "column from b and keeps it in the matrix (a double count), which has no oracle")
+    if not mask.any():
+        return np.zeros(mask.shape)  # physics.py:275-276
+    kw = {"rhs": src[0]} if force_field is None else {"force_field": src}
+    x, st = _ctx().poisson_solve(mask, float(dx), float(dy), float(dz), dirichlet=dm, wall_bc=wall_bc, **kw)
+    solve_poisson.last_stats = st
+    return x

@@ -28,7 +28,18 @@ The result always carries ``Fx``, ``Fy``, ``Fz`` (and ``Mx``, ``My``, ``Mz`` wit
 which the reference's staircase leaves out.  The permeability is the reference's expression of the
 device's float64 sums of u, v, w and of ``np.gradient(pressure)``'s components.
 
-``compute_pressure_field`` and ``compute_interface_drag_mesh`` stay with the reference.
+``compute_pressure_field`` (:190-330) runs on the GPU as one resident chain (csrc/ptv_pressure.hip
+behind ``ptv_pressure_recover``): the mask-aware Laplacian with its two fill rounds,
+the force field, the force divergence and the Poisson solve, CG for an anchored solve and the LSQR
+of the projection cleaning for ``anchor='none'``.  The force field and the divergence are
+bit-identical to the reference; the pressure agrees normwise (a Krylov solve summed in another
+order).  Two extensions: ``mask=None`` means all fluid (the reference raises on it in every
+branch), and float32 fields are widened exactly and computed in float64, so the result is float64
+(the reference would compute them in float32).  ``recover_pressure`` is the same computation with
+the solver settings exposed and the statistics returned; ``compute_force_field`` stops after the
+force field.
+
+``compute_interface_drag_mesh`` stays with the reference.
 """
 from __future__ import annotations
 
@@ -37,7 +48,8 @@ import numpy as np
 from . import _lib, launcher
 
 __all__ = ["compute_strain_rate", "compute_viscous_dissipation", "compute_vorticity", "compute_permeability",
-           "compute_astarita_flow_type", "analyze", "compute_interface_drag", "compute_permeability_from_pressure"]
+           "compute_astarita_flow_type", "analyze", "compute_interface_drag", "compute_permeability_from_pressure",
+           "compute_pressure_field", "recover_pressure", "compute_force_field"]
 
 # np.gradient's message for an axis shorter than edge_order + 1
 _TOO_SMALL = ("Shape of array too small to calculate a numerical gradient, at least (edge_order + 1) elements "
@@ -322,3 +334,78 @@ def compute_permeability_from_pressure(u, v, w, pressure, viscosity, dx, dy, dz)
     _, st = ctx.flow_analysis(*fields, hx, hy, hz, outputs=())
     gz, gy, gx = ctx.gradient_sums(p, hx, hy, hz, spacing_strong=strong)
     return _permeability_from_pressure(st["sum_u"], st["sum_v"], st["sum_w"], gx, gy, gz, st["n_voxels"], viscosity)
+
+
+# ---- pressure recovery (velocity_analysis.py:190-330) ----
+def _pressure_args(u, v, w, dx, dy, dz, mu, rho, mask):
+    """Validation shared by the pressure entry points, before any device call: the fields as
+    float64 (float32 and integer fields widen exactly), the mask as bool (None = all fluid)."""
+    u, v, w = (np.asarray(a) for a in (u, v, w))
+    if not (u.shape == v.shape == w.shape) or u.ndim != 3:
+        raise ValueError(f"u, v and w must share one 3-D shape, got {u.shape}, {v.shape}, {w.shape}")
+    for a in (u, v, w):
+        if a.dtype.kind not in "biuf" or a.dtype.itemsize > 8:
+            raise NotImplementedError(f"field dtype {a.dtype} (GPU path: float32 / float64)")
+    if mask is None:
+        mask = np.ones(u.shape, dtype=bool)
+    mask = _mask_arg(mask, u.shape)
+    _scalar_args(dx, dy, dz, mu)
+    if np.ndim(rho) != 0 or not np.isfinite(rho):
+        raise ValueError(f"rho must be a finite scalar, got {rho!r}")
+    if rho > 0 and min(u.shape) < 2:
+        raise ValueError(_TOO_SMALL)
+    return [a.astype(np.float64, copy=False) for a in (u, v, w)], mask
+
+
+def _solve_args(wall_bc, anchor):
+    if wall_bc not in _lib.WALL_BC:
+        raise ValueError(f"unknown wall_bc {wall_bc!r} (one of {sorted(_lib.WALL_BC)})")
+    if anchor not in _lib.ANCHOR:
+        raise ValueError(f"unknown anchor {anchor!r} (one of {sorted(_lib.ANCHOR)})")
+
+
+def compute_force_field(u, v, w, dx, dy, dz, mu, rho=0, mask=None):
+    """velocity_analysis.py:210-289 on the GPU: ``mu * laplacian_mask_aware(vel)``, minus
+    ``rho * (vel . grad) vel`` for ``rho > 0``; returns ``(fx, fy, fz)``, float64, bit-identical to
+    the reference at every voxel."""
+    fields, mask = _pressure_args(u, v, w, dx, dy, dz, mu, rho, mask)
+    if mask.size == 0:
+        return tuple(np.zeros(mask.shape) for _ in range(3))
+    f, st = _ctx().force_field(*fields, mask, float(dx), float(dy), float(dz), float(mu), float(rho))
+    compute_force_field.last_stats = st
+    return f
+
+
+def recover_pressure(u, v, w, dx, dy, dz, mu, rho=0, mask=None, wall_bc='zero-neumann', anchor='outlet',
+                     flow_direction='auto', rtol=1e-10, maxiter=3000):
+    """``compute_pressure_field`` without the report, with the CG settings exposed; returns
+    ``(p, stats)``.  ``stats`` carries ``itn``, ``info`` (CG: scipy's; ``anchor='none'``: lsqr's
+    istop), ``bnorm``, ``rnorm``, the sums of |fx|, |fy|, |fz| and w over the fluid voxels,
+    ``n_fluid``, ``n_dirichlet``, ``anchor_plane`` and the device times."""
+    fields, mask = _pressure_args(u, v, w, dx, dy, dz, mu, rho, mask)
+    _solve_args(wall_bc, anchor)
+    if not np.isfinite(rtol) or int(maxiter) != maxiter or maxiter < 0:
+        raise ValueError(f"rtol must be finite and maxiter an integer >= 0, got {rtol!r}, {maxiter!r}")
+    if flow_direction not in ("positive", "negative"):
+        flow_direction = "auto"  # the reference's else branch (:310)
+    if mask.size == 0:
+        return np.zeros(mask.shape), {"n_fluid": 0}
+    return _ctx().pressure_recover(*fields, mask, float(dx), float(dy), float(dz), float(mu), float(rho), wall_bc,
+                                   anchor, flow_direction, rtol=float(rtol), maxiter=int(maxiter))
+
+
+def compute_pressure_field(u, v, w, dx, dy, dz, mu, rho=0, mask=None, wall_bc='zero-neumann', anchor='outlet', flow_direction='auto'):
+    """velocity_analysis.py:190-330 on the GPU: the relative pressure from the pressure Poisson
+    equation; prints the reference's report.  ``mask=None`` means all fluid; the result is float64."""
+    p, st = recover_pressure(u, v, w, dx, dy, dz, mu, rho, mask, wall_bc, anchor, flow_direction)
+    print(f"Computing pressure field source term (mu={mu}, rho={rho}, wall_bc={wall_bc}, flow={flow_direction})...")
+    n = np.float64(st["n_fluid"])
+    with np.errstate(invalid="ignore"):  # a mask without fluid: the reference's means of nothing are NaN
+        means = [np.float64(st.get(k, 0.0)) / n for k in ("sum_abs_fx", "sum_abs_fy", "sum_abs_fz")]
+    print(f"  Force field stats (SI):")
+    print(f"    Fx: mean={means[0]: .4e}")
+    print(f"    Fy: mean={means[1]: .4e}")
+    print(f"    Fz: mean={means[2]: .4e}")
+    print(f"Solving pressure Poisson equation (anchor={anchor} at Z-plane, dir={flow_direction})...")
+    compute_pressure_field.last_stats = st
+    return p

@@ -1,8 +1,8 @@
 """Repo-root shim for the reference ``velocity_analysis`` module (drop-in, in the manner of the root
 ``physics.py``).
 
-The reference module holds more than the flow analysis: ``compute_pressure_field`` and the mesh
-interface drag stay on the host, and by default so do ``compute_interface_drag`` and
+The reference module holds more than the flow analysis: the mesh interface drag stays on the host,
+and by default so do ``compute_pressure_field``, ``compute_interface_drag`` and
 ``compute_permeability_from_pressure``.  When the reference ``velocity_analysis.py`` is on the path
 (next to the caller's script), it is loaded under a private name and every one of its names is
 re-exported; ``compute_strain_rate``, ``compute_viscous_dissipation``, ``compute_vorticity``,
@@ -19,8 +19,13 @@ The GPU drag agrees with the reference to the rounding of a reordered sum and ad
 ``Fy``, ``Fz`` (``Mx``, ``My``, ``Mz`` with a volume) that the reference's staircase leaves out
 (INTEGRATION.md).
 
-Without the reference module (the GPU box), the five functions, ``analyze`` and the two GPU
-functions above are provided.
+With ``PTV_GPU_PRESSURE=1``, independently, ``compute_pressure_field`` (:190-330) is replaced in the
+same way.  The GPU pressure agrees with the reference normwise (its force field and right-hand side
+bit for bit); it does not need the ``tol=`` keyword that scipy 1.14 removed from
+``cg``, which the reference's ``solve_poisson`` still passes.
+
+Without the reference module (the GPU box), the five functions, ``analyze``, the two drag functions
+above, ``compute_pressure_field``, ``recover_pressure`` and ``compute_force_field`` are provided.
 
 This module is found instead of the reference's when the repository root precedes the reference's
 directory on ``sys.path``.  A script started from inside the reference's directory
@@ -35,6 +40,7 @@ from ptv_interpolation_amd import velocity_analysis as _gpu
 _NAMES = ("compute_strain_rate", "compute_viscous_dissipation", "compute_vorticity", "compute_permeability",
           "compute_astarita_flow_type")
 _DRAG_NAMES = ("compute_interface_drag", "compute_permeability_from_pressure")
+_PRESSURE_NAMES = ("compute_pressure_field", "recover_pressure", "compute_force_field")
 _ROOT = _os.path.dirname(_os.path.abspath(__file__))
 
 
@@ -92,3 +98,10 @@ elif _os.environ.get("PTV_GPU_DRAG") == "1":
     for _n, _f in _new.items():
         globals()[_n] = _f
         setattr(_ref, _n, _f)
+
+if _ref is None:
+    for _n in _PRESSURE_NAMES:
+        globals()[_n] = getattr(_gpu, _n)
+elif _os.environ.get("PTV_GPU_PRESSURE") == "1":
+    compute_pressure_field = _gpu.compute_pressure_field
+    _ref.compute_pressure_field = _gpu.compute_pressure_field
