@@ -497,6 +497,64 @@ typedef struct {
     double ms_total;
 } ptv_pressure_stats;
 
+/*
+ * Cubic B-spline sampling and the mesh interface drag (scipy.ndimage.spline_filter and
+ * map_coordinates with mode='nearest'; velocity_analysis.compute_interface_drag_mesh from the
+ * triangulation onward, velocity_analysis.py:547-655).  Fields are (nz, ny, nx) C order.
+ *   prefilter     the float64 cubic B-spline coefficients of the field padded by PTV_SPLINE_PAD
+ *                 edge-replicated samples on every side, (nz + 24, ny + 24, nx + 24): what scipy
+ *                 builds for mode='nearest' (np.pad(..., 12, mode='edge'), then spline_filter(...,
+ *                 3, mode='nearest')).  Along axis 0, 1, 2 in turn, on the padded length n, with
+ *                 the pole z = sqrt(3) - 2: the line times (1 - z)(1 - 1/z); scipy's reflect start
+ *                 c0 += z / (1 - z^2n) * (c0 + z^n c[n-1] + sum_i z^i (c[i] + z^n c[n-1-i])), the
+ *                 sum cut after PTV_SPLINE_HORIZON terms (|z|^40 = 1.3e-23); c[i] += z c[i-1];
+ *                 c[n-1] *= z / (z - 1); c[i] = z (c[i+1] - c[i]).
+ *   sampling      coordinates are (3, n_points) float64 rows z, y, x in index units.
+ *                 order 3: at coordinate + 12 in the padded coefficients, clamped to the padded
+ *                 extent only, weights ((1-t)^3, 3t^3 - 6t^2 + 4, -3t^3 + 3t^2 + 3t + 1, t^3) / 6 on
+ *                 the 4 x 4 x 4 block from floor(x) - 1 (indices clamped to the padded extent).
+ *                 order 1: trilinear on the raw field, the coordinate clamped to [0, n - 1].
+ *                 order 0: the sample at floor(x + 0.5) clamped to [0, n - 1].
+ *                 A NaN coordinate gives NaN (orders 1, 3) or reads index 0 (order 0).
+ *   mesh drag     per triangle the reference's terms in its own arithmetic (the centroid and the
+ *                 edge differences in the vertices' dtype, everything else float64), summed per
+ *                 label in a fixed order (no atomics): the same bits on every call.
+ * PTV_API_VERSION is not raised: the presence of ptv_abi_sizes10 is the capability probe.
+ */
+#define PTV_SPLINE_PAD 12
+#define PTV_SPLINE_HORIZON 40
+typedef struct {
+    int64_t nx, ny, nz;  /* the raw field, positive */
+    int field_dtype;     /* PTV_F64 | PTV_F32 (widened exactly on load) */
+    int order;           /* ptv_map_coordinates: 0, 1 or 3 */
+    int64_t n_points;    /* ptv_map_coordinates: >= 0 */
+} ptv_spline_params;
+
+/* The sums of one label, in the order of the reference's result (velocity_analysis.py:621-643). */
+#define PTV_MESH_SUMS 21
+typedef struct {
+    int64_t nx, ny, nz;         /* the fields, positive */
+    int field_dtype;            /* PTV_F64 | PTV_F32: u, v, w and the pressure */
+    int vert_dtype;             /* PTV_F64 | PTV_F32: the vertices (skimage's are float32) */
+    int64_t n_verts, n_tris;    /* of all labels together; n_tris >= 1 */
+    int n_labels;               /* >= 1 */
+    double dx, dy, dz;          /* positive and finite */
+    double viscosity;           /* finite */
+    int reuse;                  /* nonzero: no prefilter, the context holds the coefficients of u, v, w from
+                                 * its last mesh drag call (the same nx, ny, nz, PTV_E_ARG otherwise); the
+                                 * host-buffer call then also keeps the fields, the pressure and the
+                                 * background mask it uploaded last and reads none of those pointers */
+    const int64_t *tri_offsets; /* n_labels + 1 ascending, [0] = 0, [n_labels] = n_tris: label l owns
+                                 * triangles [tri_offsets[l], tri_offsets[l + 1]); HOST memory in both calls */
+} ptv_mesh_params;
+
+/* sums: Fx_v Fy_v Fz_v, Fx_v_tan Fy_v_tan Fz_v_tan, Fx_v_nor Fy_v_nor Fz_v_nor, Fx_p Fy_p Fz_p, Area,
+ * Fx_water Fy_water Fz_water, Fx_solid Fy_solid Fz_solid, Area_water, Area_solid. */
+typedef struct {
+    int64_t n_tris;
+    double sums[PTV_MESH_SUMS];
+} ptv_mesh_record;
+
 /* Library / device management. */
 int ptv_version(void);
 /* sizeof(ptv_particles, ptv_grid, ptv_knn_params, ptv_stats, ptv_rbf_params, ptv_div_params):
@@ -524,6 +582,9 @@ int ptv_abi_sizes8(int64_t out4[4]);
 /* sizeof(ptv_pressure_params, ptv_pressure_stats): the same self-check.  A library that has this
  * symbol has the pressure recovery entry points (PTV_API_VERSION stays 11). */
 int ptv_abi_sizes9(int64_t out2[2]);
+/* sizeof(ptv_spline_params, ptv_mesh_params, ptv_mesh_record): the same self-check.  A library that
+ * has this symbol has the spline sampling and mesh drag entry points (PTV_API_VERSION stays 11). */
+int ptv_abi_sizes10(int64_t out3[3]);
 const char *ptv_last_error(void);
 int ptv_device_count(int *out);
 int ptv_init(int device, ptv_ctx **out);
@@ -838,6 +899,51 @@ int ptv_pressure_recover(ptv_ctx *ctx, const ptv_pressure_params *prm, const dou
 /* Same on device pointers, enqueued on `stream`; synchronises.  P may alias none of the inputs. */
 int ptv_pressure_recover_dev(ptv_ctx *ctx, const ptv_pressure_params *prm, const double *U, const double *V,
                              const double *W, double *P, void *stream, ptv_pressure_stats *st);
+
+/*
+ * Cubic B-spline prefilter, host buffers: H2D of the field, the three passes, D2H of the
+ * (nz + 24) * (ny + 24) * (nx + 24) float64 coefficients.  Reads nx, ny, nz and field_dtype of prm.
+ * ms (may be NULL) receives the kernels' time, hipEvent based.
+ */
+int ptv_spline_prefilter(ptv_ctx *ctx, const ptv_spline_params *prm, const void *field, double *coef, double *ms);
+
+/* Same on device pointers, enqueued on `stream` (NULL = the ctx's own); synchronises (for ms).
+ * coef must not alias field. */
+int ptv_spline_prefilter_dev(ptv_ctx *ctx, const ptv_spline_params *prm, const void *field, double *coef,
+                             void *stream, double *ms);
+
+/*
+ * out[i] = the order-prm->order sample of the field at (coords[i], coords[n_points + i],
+ * coords[2 * n_points + i]) = (z, y, x), host buffers.  Order 3 filters the field into the context's
+ * coefficient buffer first; field == NULL samples the coefficients the last order-3 call left there
+ * (the same nx, ny, nz, PTV_E_ARG otherwise), so that repeated calls on one field filter it once.
+ * Orders 0 and 1 read the raw field.  ms (may be NULL): the kernels' time.
+ */
+int ptv_map_coordinates(ptv_ctx *ctx, const ptv_spline_params *prm, const void *field, const double *coords,
+                        double *out, double *ms);
+
+/* Same on device pointers, enqueued on `stream` (NULL = the ctx's own); synchronises (for ms). */
+int ptv_map_coordinates_dev(ptv_ctx *ctx, const ptv_spline_params *prm, const void *field, const double *coords,
+                            double *out, void *stream, double *ms);
+
+/*
+ * Mesh interface drag, host buffers: H2D of the fields, one prefilter each of U, V, W into the
+ * context's coefficient buffers, one launch over all labels' triangles, D2H of one record per
+ * label.  P (the pressure, field_dtype) may be NULL (its samples are 0); bg (uint8, nonzero = pore
+ * space) may be NULL (every triangle is 'water').  verts: (n_verts, 3) as z, y, x in index units;
+ * faces: (n_tris, 3) int32 indices into verts (checked here).  ms2 (may be NULL) receives the
+ * prefilters' and the traction kernels' times.
+ */
+int ptv_mesh_drag(ptv_ctx *ctx, const ptv_mesh_params *prm, const void *U, const void *V, const void *W,
+                  const void *P, const uint8_t *bg, const void *verts, const int32_t *faces,
+                  ptv_mesh_record *records, double ms2[2]);
+
+/* Same on device pointers (fields, bg, verts, faces; prm->tri_offsets and records stay host memory),
+ * enqueued on `stream` (NULL = the ctx's own); synchronises (the records are returned).  A face
+ * index outside [0, n_verts) reads the nearest valid vertex. */
+int ptv_mesh_drag_dev(ptv_ctx *ctx, const ptv_mesh_params *prm, const void *U, const void *V, const void *W,
+                      const void *P, const uint8_t *bg, const void *verts, const int32_t *faces, void *stream,
+                      ptv_mesh_record *records, double ms2[2]);
 
 /*
  * Last-launch k-NN kernel duration in ms (hipEvent pair recorded around the

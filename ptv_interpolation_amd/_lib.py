@@ -179,6 +179,32 @@ class DragStats(C.Structure):
 DRAG_RECORD = np.dtype([("count", np.int64), ("sum_p", np.float64), ("sum_u", np.float64), ("sum_v", np.float64),
                         ("sum_w", np.float64)])
 
+class SplineParams(C.Structure):
+    _fields_ = [("nx", C.c_int64), ("ny", C.c_int64), ("nz", C.c_int64), ("field_dtype", C.c_int), ("order", C.c_int),
+                ("n_points", C.c_int64)]
+
+
+SPLINE_PAD = 12  # PTV_SPLINE_PAD: edge-replicated samples on every side of the coefficient array
+# the sums of one label in the order of the reference's result (velocity_analysis.py:621-643)
+MESH_KEYS = ("Fx_v", "Fy_v", "Fz_v", "Fx_v_tan", "Fy_v_tan", "Fz_v_tan", "Fx_v_nor", "Fy_v_nor", "Fz_v_nor",
+             "Fx_p", "Fy_p", "Fz_p", "Area", "Fx_water", "Fy_water", "Fz_water", "Fx_solid", "Fy_solid", "Fz_solid",
+             "Area_water", "Area_solid")
+
+
+class MeshParams(C.Structure):
+    _fields_ = [("nx", C.c_int64), ("ny", C.c_int64), ("nz", C.c_int64), ("field_dtype", C.c_int),
+                ("vert_dtype", C.c_int), ("n_verts", C.c_int64), ("n_tris", C.c_int64), ("n_labels", C.c_int),
+                ("dx", C.c_double), ("dy", C.c_double), ("dz", C.c_double), ("viscosity", C.c_double),
+                ("reuse", C.c_int), ("tri_offsets", C.POINTER(C.c_int64))]
+
+
+class MeshRecord(C.Structure):
+    """The triangle count and the sums (MESH_KEYS) of one label of the mesh drag."""
+    _fields_ = [("n_tris", C.c_int64), ("sums", C.c_double * len(MESH_KEYS))]
+
+
+MESH_RECORD = np.dtype([("n_tris", np.int64), ("sums", np.float64, (len(MESH_KEYS),))])
+
 WALL_BC = {"zero-neumann": 0, "inhomogeneous": 1}  # PTV_WALL_*
 ANCHOR = {"none": 0, "outlet": 1, "inlet": 2}      # PTV_ANCHOR_*
 FLOW_DIRECTION = {"auto": 0, "positive": 1, "negative": -1}
@@ -340,6 +366,13 @@ EXPORTS = {
                              [C.POINTER(PressureStats)]),
     "ptv_pressure_recover_dev": (C.c_int, [C.c_void_p, C.POINTER(PressureParams)] + [_dp] * 4 +
                                  [C.c_void_p, C.POINTER(PressureStats)]),
+    "ptv_abi_sizes10": (C.c_int, [C.POINTER(C.c_int64)]),
+    "ptv_spline_prefilter": (C.c_int, [C.c_void_p, C.POINTER(SplineParams)] + [C.c_void_p] * 2 + [_dp]),
+    "ptv_spline_prefilter_dev": (C.c_int, [C.c_void_p, C.POINTER(SplineParams)] + [C.c_void_p] * 3 + [_dp]),
+    "ptv_map_coordinates": (C.c_int, [C.c_void_p, C.POINTER(SplineParams)] + [C.c_void_p] * 3 + [_dp]),
+    "ptv_map_coordinates_dev": (C.c_int, [C.c_void_p, C.POINTER(SplineParams)] + [C.c_void_p] * 4 + [_dp]),
+    "ptv_mesh_drag": (C.c_int, [C.c_void_p, C.POINTER(MeshParams)] + [C.c_void_p] * 8 + [_dp]),
+    "ptv_mesh_drag_dev": (C.c_int, [C.c_void_p, C.POINTER(MeshParams)] + [C.c_void_p] * 9 + [_dp]),
     "ptv_last_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     "ptv_debug_stamps": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double)]),
 }
@@ -470,6 +503,13 @@ def abi_sizes9():
     out = (C.c_int64 * 2)()
     check(lib().ptv_abi_sizes9(out))
     return list(out), [C.sizeof(PressureParams), C.sizeof(PressureStats)]
+
+
+def abi_sizes10():
+    """(C sizeof, ctypes sizeof) of ptv_spline_params, ptv_mesh_params and ptv_mesh_record."""
+    out = (C.c_int64 * 3)()
+    check(lib().ptv_abi_sizes10(out))
+    return list(out), [C.sizeof(SplineParams), C.sizeof(MeshParams), C.sizeof(MeshRecord)]
 
 
 def edt_check_shape(shape):
@@ -1366,6 +1406,133 @@ class Context:
         """The same for points and a distance field resident in HBM (device pointers)."""
         return self._align_call(lib().ptv_align_score_dev, shape, n_points, [points_ptr, dt_ptr], offsets,
                                 extra=(C.c_void_p(stream or 0),))
+
+    # -- cubic B-spline sampling and the mesh interface drag (velocity_analysis.py:513-657) ----
+    @staticmethod
+    def _spline_field(field):
+        f = np.ascontiguousarray(field)
+        if f.ndim != 3 or f.dtype not in (np.float32, np.float64):
+            raise ValueError(f"a 3-D float32 / float64 field, got {f.ndim}-D {f.dtype}")
+        return f, (F32 if f.dtype == np.float32 else F64)
+
+    def spline_prefilter(self, field):
+        """The float64 cubic B-spline coefficients of a host float32 / float64 (nz, ny, nx) field padded
+        by SPLINE_PAD edge-replicated samples per side: scipy's ``spline_filter(np.pad(field, 12,
+        mode='edge'), 3, mode='nearest')``.  Returns ``(coefficients, ms)``."""
+        f, dt = self._spline_field(field)
+        nz, ny, nx = f.shape
+        coef = np.empty((nz + 2 * SPLINE_PAD, ny + 2 * SPLINE_PAD, nx + 2 * SPLINE_PAD), dtype=np.float64)
+        prm = SplineParams(nx, ny, nz, dt, 3, 0)
+        ms = C.c_double(0.0)
+        check(lib().ptv_spline_prefilter(self.h, C.byref(prm), f.ctypes.data_as(C.c_void_p),
+                                         coef.ctypes.data_as(C.c_void_p), C.byref(ms)))
+        return coef, ms.value
+
+    def spline_prefilter_dev(self, nx, ny, nz, field_ptr, coef_ptr, field_dtype=F64, stream=0):
+        """The same for a field resident in HBM into a device buffer of (nz + 24)(ny + 24)(nx + 24)
+        float64.  Returns the kernels' time."""
+        prm = SplineParams(nx, ny, nz, int(field_dtype), 3, 0)
+        ms = C.c_double(0.0)
+        check(lib().ptv_spline_prefilter_dev(self.h, C.byref(prm), C.c_void_p(field_ptr), C.c_void_p(coef_ptr),
+                                             C.c_void_p(stream or 0), C.byref(ms)))
+        return ms.value
+
+    def map_coordinates(self, field, coordinates, order=3, shape=None):
+        """Samples of a host (nz, ny, nx) field at ``coordinates`` (3, n) float64 rows z, y, x, as
+        scipy's ``map_coordinates(field, coordinates, order=order, mode='nearest')`` for order 0, 1
+        or 3.  An order-3 call filters the field into the context; ``field`` None (with ``shape``)
+        samples the coefficients the last order-3 call left.  Returns ``(samples, ms)``."""
+        co = np.ascontiguousarray(coordinates, dtype=np.float64)
+        if co.ndim != 2 or co.shape[0] != 3:
+            raise ValueError(f"coordinates must be (3, n), got {co.shape}")
+        if field is None:
+            nz, ny, nx = (int(n) for n in shape)
+            f, dt = None, F64
+        else:
+            f, dt = self._spline_field(field)
+            nz, ny, nx = f.shape
+        out = np.empty(co.shape[1], dtype=np.float64)
+        prm = SplineParams(nx, ny, nz, dt, int(order), co.shape[1])
+        ms = C.c_double(0.0)
+        check(lib().ptv_map_coordinates(self.h, C.byref(prm), None if f is None else f.ctypes.data_as(C.c_void_p),
+                                        co.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), C.byref(ms)))
+        return out, ms.value
+
+    def map_coordinates_dev(self, nx, ny, nz, field_ptr, coords_ptr, n_points, out_ptr, order=3, field_dtype=F64,
+                            stream=0):
+        """The same on device pointers (``field_ptr`` 0: the resident coefficients, order 3 only);
+        coordinates (3, n) and samples (n,) float64 in HBM.  Returns the kernels' time."""
+        prm = SplineParams(nx, ny, nz, int(field_dtype), int(order), int(n_points))
+        ms = C.c_double(0.0)
+        check(lib().ptv_map_coordinates_dev(self.h, C.byref(prm), C.c_void_p(field_ptr) if field_ptr else None,
+                                            C.c_void_p(coords_ptr), C.c_void_p(out_ptr), C.c_void_p(stream or 0),
+                                            C.byref(ms)))
+        return ms.value
+
+    def _mesh_call(self, fn, shape, ptrs, tri_offsets, n_verts, field_dtype, vert_dtype, viscosity, dx, dy, dz, reuse,
+                   extra=()):
+        off = np.ascontiguousarray(tri_offsets, dtype=np.int64).reshape(-1)
+        nz, ny, nx = shape
+        prm = MeshParams(nx, ny, nz, int(field_dtype), int(vert_dtype), int(n_verts), int(off[-1]), int(off.size - 1),
+                         float(dx), float(dy), float(dz), float(viscosity), int(bool(reuse)),
+                         off.ctypes.data_as(C.POINTER(C.c_int64)))
+        rec = np.zeros(off.size - 1, dtype=MESH_RECORD)
+        ms = (C.c_double * 2)()
+        check(fn(self.h, C.byref(prm), *[C.c_void_p(p) if p else None for p in ptrs], *extra,
+                 rec.ctypes.data_as(C.c_void_p), ms))
+        return rec, {"ms_prefilter": ms[0], "ms_traction": ms[1]}
+
+    def mesh_drag(self, fields, pressure, background, verts, faces, tri_offsets, viscosity, dx, dy, dz, shape=None):
+        """Mesh interface drag of host arrays.  ``fields``: u, v, w of one float32 / float64 dtype,
+        (nz, ny, nx); ``pressure`` (the same dtype) and ``background`` (uint8 / bool, nonzero = pore
+        space) may be None.  ``verts`` (n, 3) float32 / float64 rows z, y, x, ``faces`` (m, 3) indices
+        into them, ``tri_offsets`` (labels + 1,): label l owns faces [tri_offsets[l],
+        tri_offsets[l + 1]).  ``fields`` None (with ``shape``): the fields, their coefficients, the
+        pressure and the background of the previous call stay as they are in the context (no upload,
+        no prefilter).  Returns ``(records, times)``: MESH_RECORD per label, and the prefilters' and
+        the traction kernels' ms."""
+        vt = np.ascontiguousarray(verts)
+        if vt.dtype not in (np.float32, np.float64):
+            vt = vt.astype(np.float64)
+        fc = np.ascontiguousarray(faces, dtype=np.int32)
+        if vt.ndim != 2 or vt.shape[1] != 3 or fc.ndim != 2 or fc.shape[1] != 3:
+            raise ValueError(f"verts (n, 3) and faces (m, 3), got {vt.shape} and {fc.shape}")
+        keep = [vt, fc]
+        if fields is None:
+            ptrs, ft, shape = [0] * 5, getattr(self, "_mesh_dtype", F64), tuple(int(n) for n in shape)
+        else:
+            f = [self._spline_field(a)[0] for a in fields]
+            ft = F32 if f[0].dtype == np.float32 else F64
+            if pressure is not None:
+                f.append(np.ascontiguousarray(pressure, dtype=f[0].dtype))
+            if len({a.shape for a in f}) != 1 or len({a.dtype for a in f}) != 1:
+                raise ValueError("u, v, w and the pressure must share one shape and dtype")
+            shape = f[0].shape
+            ptrs = [a.ctypes.data for a in f] + [0] * (4 - len(f))
+            if background is not None:
+                bg = np.ascontiguousarray(background).view(np.uint8) if np.asarray(background).dtype == np.bool_ \
+                    else np.ascontiguousarray(background, dtype=np.uint8)
+                if bg.shape != shape:
+                    raise ValueError(f"background shape {bg.shape} does not match the fields' {shape}")
+                keep.append(bg)
+                ptrs.append(bg.ctypes.data)
+            else:
+                ptrs.append(0)
+            keep.append(f)
+        res = self._mesh_call(lib().ptv_mesh_drag, shape, ptrs + [vt.ctypes.data, fc.ctypes.data], tri_offsets,
+                              vt.shape[0], ft, F32 if vt.dtype == np.float32 else F64, viscosity, dx, dy, dz,
+                              reuse=fields is None)
+        self._mesh_dtype = ft
+        return res
+
+    def mesh_drag_dev(self, nx, ny, nz, ptrs, pressure_ptr, background_ptr, verts_ptr, n_verts, faces_ptr, tri_offsets,
+                      viscosity, dx, dy, dz, field_dtype=F64, vert_dtype=F32, reuse=False, stream=0):
+        """Device-pointer mesh drag: u, v, w (``ptrs``), the pressure and the uint8 background (0 =
+        none), the vertices and the int32 faces resident in HBM; ``tri_offsets`` and the records stay on
+        the host.  ``reuse``: skip the prefilters, the context holds these fields' coefficients."""
+        return self._mesh_call(lib().ptv_mesh_drag_dev, (nz, ny, nx),
+                               [*ptrs, pressure_ptr, background_ptr, verts_ptr, faces_ptr], tri_offsets, n_verts,
+                               field_dtype, vert_dtype, viscosity, dx, dy, dz, reuse, extra=(C.c_void_p(stream or 0),))
 
 
 class AlignSession:

@@ -128,6 +128,17 @@ int ptv_abi_sizes9(int64_t out2[2]) {
     return PTV_OK;
 }
 
+int ptv_abi_sizes10(int64_t out3[3]) {
+    if (!out3) {
+        set_error("ptv_abi_sizes10: out is NULL");
+        return PTV_E_ARG;
+    }
+    out3[0] = (int64_t)sizeof(ptv_spline_params);
+    out3[1] = (int64_t)sizeof(ptv_mesh_params);
+    out3[2] = (int64_t)sizeof(ptv_mesh_record);
+    return PTV_OK;
+}
+
 const char *ptv_last_error(void) { return g_last_error.c_str(); }
 
 int ptv_device_count(int *out) {

@@ -13,6 +13,7 @@
 #include "ptv_clean.hpp"
 #include "ptv_kernels.hpp"
 #include "ptv_knn_big.hpp"
+#include "ptv_mesh.hpp"
 #include "ptv_own.hpp"
 #include "ptv_pressure.hpp"
 #include "ptv_variational.hpp"
@@ -119,6 +120,19 @@ struct ptv_ctx {
     ptv::DevBuf<int> align_pcnt;                                      //   and inside counts
     ptv::DevBuf<ptv_align_record> align_rec;                          // one record per offset
     ptv::Event ev_edt0, ev_edt1;                                      // around the kernels of either
+    ptv::DevBuf<double> spl_coef;                                     // map_coordinates: resident coefficients
+    int64_t spl_dims[3] = {0, 0, 0};                                  //   what they hold (nx, ny, nz; 0: nothing)
+    ptv::DevBuf<uint8_t> spl_fld;                                     // its host calls: the field,
+    ptv::DevBuf<double> spl_pts, spl_out;                             //   coordinates, samples / coefficients
+    ptv::DevBuf<double> mesh_coef[3];                                 // mesh drag: resident coefficients of U, V, W
+    int64_t mesh_dims[3] = {0, 0, 0};                                 //   what they hold (nx, ny, nz; 0: nothing)
+    ptv::DevBuf<uint8_t> mesh_fld[4], mesh_bg, mesh_verts;            // its host calls: U, V, W, P, mask, vertices
+    int mesh_fld_dtype = -1;                                          //   what the resident fields are
+    bool mesh_has_p = false, mesh_has_bg = false;                     //   (-1: nothing)
+    ptv::DevBuf<int32_t> mesh_faces, mesh_blk_label;                  // faces (host calls); block -> label slot
+    ptv::DevBuf<int64_t> mesh_blk_first, mesh_lab_blk0, mesh_off;     // block -> first triangle; per-label tables
+    ptv::DevBuf<double> mesh_part, mesh_res;                          // per-block partials, per-label sums
+    ptv::Event ev_mesh[3];                                            // prefilter start, traction start, end
     ptv::PinnedBuf<double> h_bbox;                                    // pinned, kHostWords doubles
     ptv::PinnedBuf<unsigned long long> h_misc;  // pinned scratch words (cull count, halo bound, repair count)
     ptv_stats last{};

@@ -39,7 +39,16 @@ branch), and float32 fields are widened exactly and computed in float64, so the 
 the solver settings exposed and the statistics returned; ``compute_force_field`` stops after the
 force field.
 
-``compute_interface_drag_mesh`` stays with the reference.
+``compute_interface_drag_mesh`` (:513-657) keeps its triangulation on the host
+(``skimage.measure.marching_cubes`` per label, ``ImportError`` without scikit-image) and integrates
+on the GPU (csrc/ptv_mesh.hip behind ``ptv_mesh_drag``): each of u, v, w goes through
+one cubic B-spline prefilter whose coefficients stay in HBM, and all labels' triangles through one
+launch that takes the order-3, order-1 and order-0 samples and forms the reference's 21 sums per
+label in a fixed order.  ``integrate_mesh_drag`` is that integration for meshes from any source.
+The sums agree with the reference to rounding (the bar of tests/test_gpu_mesh.py); float32 and
+integer fields are widened exactly and computed in float64.  ``compute_interface_drag`` keeps
+raising ``NotImplementedError`` for ``method='mesh'``: the root shim's ``PTV_GPU_DRAG_MESH=1`` routes
+that method here.
 """
 from __future__ import annotations
 
@@ -49,7 +58,8 @@ from . import _lib, launcher
 
 __all__ = ["compute_strain_rate", "compute_viscous_dissipation", "compute_vorticity", "compute_permeability",
            "compute_astarita_flow_type", "analyze", "compute_interface_drag", "compute_permeability_from_pressure",
-           "compute_pressure_field", "recover_pressure", "compute_force_field"]
+           "compute_pressure_field", "recover_pressure", "compute_force_field", "integrate_mesh_drag",
+           "compute_interface_drag_mesh"]
 
 # np.gradient's message for an axis shorter than edge_order + 1
 _TOO_SMALL = ("Shape of array too small to calculate a numerical gradient, at least (edge_order + 1) elements "
@@ -409,3 +419,133 @@ def compute_pressure_field(u, v, w, dx, dy, dz, mu, rho=0, mask=None, wall_bc='z
     print(f"Solving pressure Poisson equation (anchor={anchor} at Z-plane, dir={flow_direction})...")
     compute_pressure_field.last_stats = st
     return p
+
+
+# ---- mesh interface drag (velocity_analysis.py:513-657) ----
+def _mesh_fields(u, v, w, pressure, background_mask):
+    """u, v, w and the pressure (or None) as float64 (float32 and integer fields widen exactly), the
+    background mask (or None) as the uint8 grid of ``background_mask.astype(float) > 0.5``."""
+    fields = [np.asarray(a) for a in (u, v, w)] + ([] if pressure is None else [np.asarray(pressure)])
+    if len({a.shape for a in fields}) != 1 or fields[0].ndim != 3:
+        raise ValueError(f"u, v, w and the pressure must share one 3-D shape, got {[a.shape for a in fields]}")
+    for a in fields:
+        if a.dtype.kind not in "biuf" or a.dtype.itemsize > 8:
+            raise NotImplementedError(f"field dtype {a.dtype} (GPU path: float32 / float64)")
+    if fields[0].size == 0:
+        raise ValueError("the fields have no voxels")
+    bg = None
+    if background_mask is not None:
+        bg = np.asarray(background_mask)
+        if bg.shape != fields[0].shape:
+            raise ValueError(f"background_mask shape {bg.shape} does not match the fields' {fields[0].shape}")
+        if bg.dtype.kind not in "biuf":
+            raise NotImplementedError(f"background_mask dtype {bg.dtype}")
+        bg = (bg.astype(float) > 0.5).view(np.uint8)
+    return [a.astype(np.float64, copy=False) for a in fields], bg
+
+
+def _mesh_arrays(meshes, shape):
+    """The labels that have triangles, their vertices and faces concatenated (faces shifted to the
+    concatenated vertices) and the per-label triangle offsets."""
+    labels, verts, faces, offsets, base = [], [], [], [0], 0
+    hi = np.asarray(shape, dtype=np.float64) - 1.0
+    for label, (vt, fc) in meshes.items():
+        vt, fc = np.asarray(vt), np.asarray(fc)
+        if fc.size == 0:
+            continue  # the reference's `continue` for a label without a surface
+        if vt.ndim != 2 or vt.shape[1] != 3 or fc.ndim != 2 or fc.shape[1] != 3:
+            raise ValueError(f"label {label!r}: verts (n, 3) and faces (m, 3), got {vt.shape} and {fc.shape}")
+        if vt.dtype not in (np.float32, np.float64):
+            raise NotImplementedError(f"label {label!r}: vertex dtype {vt.dtype} (GPU path: float32 / float64)")
+        if fc.dtype.kind not in "iu":
+            raise NotImplementedError(f"label {label!r}: face dtype {fc.dtype} (GPU path: integers)")
+        if fc.min() < 0 or fc.max() >= len(vt):
+            raise ValueError(f"label {label!r}: a face index lies outside the {len(vt)} vertices")
+        used = vt[np.unique(fc)]
+        if not (np.all(used >= 0.0) and np.all(used <= hi)):  # also rejects NaN
+            raise ValueError(f"label {label!r}: vertices outside the volume [0, n - 1] (marching cubes produces none)")
+        labels.append(label)
+        verts.append(vt)
+        faces.append(fc.astype(np.int64) + base)
+        base += len(vt)
+        offsets.append(offsets[-1] + len(fc))
+    if len({vt.dtype for vt in verts}) > 1:
+        raise NotImplementedError("meshes of mixed vertex dtypes are not supported on the GPU path")
+    if base >= 2**31:
+        raise NotImplementedError("2^31 or more vertices are not supported on the GPU path")
+    return labels, verts, faces, np.asarray(offsets, dtype=np.int64)
+
+
+def _assemble_mesh(labels, records, volume=None):
+    """The reference's result dict (:620-655) from one MESH_RECORD per label."""
+    results = {}
+    for label, rec in zip(labels, records):
+        r = {k: np.float64(s) for k, s in zip(_lib.MESH_KEYS, rec["sums"])}
+        for c in "xyz":
+            r[f"F{c}"] = r[f"F{c}_v"] + r[f"F{c}_p"]
+        if volume:
+            for c in "xyz":
+                r[f"M{c}"] = r[f"F{c}"] / volume
+        results[label] = r
+    return results
+
+
+def integrate_mesh_drag(meshes, u, v, w, pressure, viscosity, dx, dy, dz, background_mask=None, volume=None,
+                        resident=False):
+    """velocity_analysis.py:547-655 on the GPU: the drag on triangulated interfaces.  ``meshes`` maps a
+    label to ``(verts, faces)``: vertices (n, 3) in voxel-index coordinates ``[z, y, x]``, float32
+    (skimage's) or float64, inside ``[0, n - 1]`` on every axis (``ValueError`` otherwise), and
+    integer faces (m, 3).  Returns the reference's dict of dicts: its 21 sums, ``Fx``, ``Fy``,
+    ``Fz``, and ``Mx``, ``My``, ``Mz`` with a truthy ``volume``; a label without triangles is left
+    out.  The fields are filtered once per call and all labels' triangles go through one launch.
+    ``resident=True``: u, v, w, the pressure and the background mask are the previous call's, still in
+    the context with their coefficients (only their shape is read here): no upload, no prefilter.
+    ``integrate_mesh_drag.last_times`` holds the device times of the last call."""
+    fields, bg = _mesh_fields(u, v, w, pressure, background_mask)
+    _scalar_args(dx, dy, dz, viscosity)
+    shape = fields[0].shape
+    labels, verts, faces, offsets = _mesh_arrays(meshes, shape)
+    if not labels:
+        return {}
+    vt, fc = np.concatenate(verts), np.concatenate(faces).astype(np.int32)
+    if resident:
+        records, times = _ctx().mesh_drag(None, None, None, vt, fc, offsets, float(viscosity), float(dx), float(dy),
+                                          float(dz), shape=shape)
+    else:
+        records, times = _ctx().mesh_drag(fields[:3], fields[3] if pressure is not None else None, bg, vt, fc, offsets,
+                                          float(viscosity), float(dx), float(dy), float(dz))
+    integrate_mesh_drag.last_times = times
+    return _assemble_mesh(labels, records, volume)
+
+
+def compute_interface_drag_mesh(u, v, w, pressure, viscosity, dx, dy, dz, mask, labels=None, mesh_step=1, volume=None, background_mask=None):
+    """velocity_analysis.py:513-657 with the integration on the GPU.  The triangulation stays on the
+    host: ``skimage.measure.marching_cubes`` per label (``ImportError`` without scikit-image; this
+    package has no staircase fallback), run on the label's bounding box grown by one voxel and
+    shifted back (the same surface as the full-volume call's, at a fraction of its cost).
+    Everything from the mesh onward is ``integrate_mesh_drag``."""
+    fields, _ = _mesh_fields(u, v, w, pressure, background_mask)
+    _scalar_args(dx, dy, dz, viscosity)
+    mask = np.asarray(mask)
+    if mask.shape != fields[0].shape:
+        raise ValueError(f"mask shape {mask.shape} does not match the fields' {fields[0].shape}")
+    from skimage import measure
+
+    if labels is None:
+        labels = np.unique(mask)
+        labels = labels[labels > 0]
+    meshes = {}
+    for label in labels:
+        where = np.nonzero(mask == label)
+        if where[0].size == 0:
+            continue
+        lo = [max(int(i.min()) - 1, 0) for i in where]
+        hi = [min(int(i.max()) + 2, n) for i, n in zip(where, mask.shape)]
+        box = (mask[lo[0]:hi[0], lo[1]:hi[1], lo[2]:hi[2]] == label).astype(float)
+        try:
+            vt, fc, _, _ = measure.marching_cubes(box, level=0.5, step_size=mesh_step)
+        except (ValueError, RuntimeError):
+            continue
+        meshes[label] = (vt + np.asarray(lo, dtype=vt.dtype), fc)
+    return integrate_mesh_drag(meshes, u, v, w, pressure, viscosity, dx, dy, dz, background_mask=background_mask,
+                               volume=volume)

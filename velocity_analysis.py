@@ -24,8 +24,15 @@ same way.  The GPU pressure agrees with the reference normwise (its force field 
 bit for bit); it does not need the ``tol=`` keyword that scipy 1.14 removed from
 ``cg``, which the reference's ``solve_poisson`` still passes.
 
+With ``PTV_GPU_DRAG_MESH=1``, independently, ``compute_interface_drag_mesh`` (:513-657) is replaced in
+the same way: marching cubes stays on the host (scikit-image is required, there is no staircase
+fallback), everything from the mesh onward runs on the GPU.  ``method='mesh'`` then reaches it
+through the reference's own dispatch, and with ``PTV_GPU_DRAG=1`` through the forwarding above.
+``integrate_mesh_drag`` (the integration for meshes from any source) is always provided.
+
 Without the reference module (the GPU box), the five functions, ``analyze``, the two drag functions
-above, ``compute_pressure_field``, ``recover_pressure`` and ``compute_force_field`` are provided.
+above, ``compute_interface_drag_mesh``, ``compute_pressure_field``, ``recover_pressure`` and
+``compute_force_field`` are provided.
 
 This module is found instead of the reference's when the repository root precedes the reference's
 directory on ``sys.path``.  A script started from inside the reference's directory
@@ -87,6 +94,14 @@ def _drag_with_host_mesh(mesh):
     compute_interface_drag.__doc__ = _gpu.compute_interface_drag.__doc__
     return compute_interface_drag
 
+
+integrate_mesh_drag = _gpu.integrate_mesh_drag
+# before the staircase opt-in, whose method='mesh' forwards to whatever the module holds by then
+if _ref is None:
+    compute_interface_drag_mesh = _gpu.compute_interface_drag_mesh
+elif _os.environ.get("PTV_GPU_DRAG_MESH") == "1":
+    compute_interface_drag_mesh = _gpu.compute_interface_drag_mesh
+    _ref.compute_interface_drag_mesh = _gpu.compute_interface_drag_mesh
 
 if _ref is None:
     for _n in _DRAG_NAMES:
