@@ -546,6 +546,12 @@ typedef struct {
                                  * background mask it uploaded last and reads none of those pointers */
     const int64_t *tri_offsets; /* n_labels + 1 ascending, [0] = 0, [n_labels] = n_tris: label l owns
                                  * triangles [tri_offsets[l], tri_offsets[l + 1]); HOST memory in both calls */
+    int mesh_resident;          /* nonzero: the mesh is the one the context's last ptv_marching_cubes left on
+                                 * the device (PTV_E_ARG if it holds none or one without a triangle): verts,
+                                 * faces, vert_dtype, n_verts, n_tris and tri_offsets are not read, n_labels
+                                 * must be that call's (PTV_E_ARG otherwise) and one record per label of that
+                                 * call is returned (n_tris 0, sums 0 for a label without a surface).  After the
+                                 * older members: a caller that zeroes the struct keeps its behaviour */
 } ptv_mesh_params;
 
 /* sums: Fx_v Fy_v Fz_v, Fx_v_tan Fy_v_tan Fz_v_tan, Fx_v_nor Fy_v_nor Fz_v_nor, Fx_p Fy_p Fz_p, Area,
@@ -554,6 +560,36 @@ typedef struct {
     int64_t n_tris;
     double sums[PTV_MESH_SUMS];
 } ptv_mesh_record;
+
+/*
+ * Marching cubes of a label mask (velocity_analysis.py:547-552 calls skimage.measure.marching_cubes per
+ * label): every requested label's indicator mask == label at level 0.5, all labels in one pass over
+ * the volume.  skimage's triangle set is NOT reproduced (on a 0/1 indicator its face tests are exact
+ * ties, and its tables are not available to this project); the triangulation follows the project's
+ * own rule, stated in DESIGN.md section 23 and pinned by tools/make_mc_table.py:
+ *   lattice     the voxels whose indices are multiples of step_size; a cube has its origin o at a
+ *               lattice point with o + step_size <= n - 1 on every axis.  No padding: a label that
+ *               touches the volume's edge has an open surface there.  An axis with n - 1 < step_size
+ *               gives no cubes and every count is 0.
+ *   vertices    one per lattice edge whose ends differ in the indicator, at its midpoint, float32
+ *               [z, y, x] in index units (exact), shared by the triangles that use it; per label in
+ *               the order of the owner lattice point (the edge's lower end; z slowest, x fastest), then
+ *               axis z, y, x.
+ *   triangles   per label by cube in the same linear order, then in the table's order; normals
+ *               cross(v1 - v0, v2 - v0) point into the label.  Faces are int32 indices into the label's
+ *               own vertices.
+ * The output is the same bytes on every call (no atomic assigns a position).  Lattice points must
+ * stay below 2^31 - 1, and so must the vertices and the triangles of all labels together
+ * (PTV_E_UNSUPPORTED).  The call synchronises twice: after the counting passes (the totals size the
+ * buffers, which are allocated then) and at the end (the counts are returned).
+ * PTV_API_VERSION is not raised: the presence of ptv_abi_sizes11 is the capability probe.
+ */
+typedef struct {
+    int64_t nx, ny, nz;    /* the mask, positive */
+    int step_size;         /* >= 1 */
+    int n_labels;          /* >= 1 */
+    const int32_t *labels; /* n_labels ascending, distinct, positive; HOST memory in both calls */
+} ptv_surface_params;
 
 /* Library / device management. */
 int ptv_version(void);
@@ -585,6 +621,9 @@ int ptv_abi_sizes9(int64_t out2[2]);
 /* sizeof(ptv_spline_params, ptv_mesh_params, ptv_mesh_record): the same self-check.  A library that
  * has this symbol has the spline sampling and mesh drag entry points (PTV_API_VERSION stays 11). */
 int ptv_abi_sizes10(int64_t out3[3]);
+/* sizeof(ptv_surface_params): the same self-check.  A library that has this symbol has the marching
+ * cubes entry points and ptv_mesh_params.mesh_resident (PTV_API_VERSION stays 11). */
+int ptv_abi_sizes11(int64_t out1[1]);
 const char *ptv_last_error(void);
 int ptv_device_count(int *out);
 int ptv_init(int device, ptv_ctx **out);
@@ -944,6 +983,24 @@ int ptv_mesh_drag(ptv_ctx *ctx, const ptv_mesh_params *prm, const void *U, const
 int ptv_mesh_drag_dev(ptv_ctx *ctx, const ptv_mesh_params *prm, const void *U, const void *V, const void *W,
                       const void *P, const uint8_t *bg, const void *verts, const int32_t *faces, void *stream,
                       ptv_mesh_record *records, double ms2[2]);
+
+/*
+ * Marching cubes, host mask (int32, (nz, ny, nx) C order).  vert_counts / tri_counts (n_labels each,
+ * host) receive the vertices and triangles per label; the mesh stays in the context until the next
+ * call.  ms2 (may be NULL): the counting passes' (classify, scans) and the emitting passes' (emit,
+ * sorts, gathers) times, hipEvent based.
+ */
+int ptv_marching_cubes(ptv_ctx *ctx, const ptv_surface_params *prm, const int32_t *mask, int64_t *vert_counts,
+                       int64_t *tri_counts, double ms2[2]);
+
+/* Same for a mask resident in HBM, enqueued on `stream` (NULL = the ctx's own). */
+int ptv_marching_cubes_dev(ptv_ctx *ctx, const ptv_surface_params *prm, const int32_t *mask, void *stream,
+                           int64_t *vert_counts, int64_t *tri_counts, double ms2[2]);
+
+/* Copies the context's mesh out: verts (sum of vert_counts, 3) float32 and faces (sum of tri_counts, 3)
+ * int32 (host), label after label; a label's faces index its own vertices.  Either may be NULL.
+ * PTV_E_ARG when the context holds no mesh. */
+int ptv_surface_fetch(ptv_ctx *ctx, float *verts, int32_t *faces);
 
 /*
  * Last-launch k-NN kernel duration in ms (hipEvent pair recorded around the

@@ -195,7 +195,7 @@ class MeshParams(C.Structure):
     _fields_ = [("nx", C.c_int64), ("ny", C.c_int64), ("nz", C.c_int64), ("field_dtype", C.c_int),
                 ("vert_dtype", C.c_int), ("n_verts", C.c_int64), ("n_tris", C.c_int64), ("n_labels", C.c_int),
                 ("dx", C.c_double), ("dy", C.c_double), ("dz", C.c_double), ("viscosity", C.c_double),
-                ("reuse", C.c_int), ("tri_offsets", C.POINTER(C.c_int64))]
+                ("reuse", C.c_int), ("tri_offsets", C.POINTER(C.c_int64)), ("mesh_resident", C.c_int)]
 
 
 class MeshRecord(C.Structure):
@@ -204,6 +204,12 @@ class MeshRecord(C.Structure):
 
 
 MESH_RECORD = np.dtype([("n_tris", np.int64), ("sums", np.float64, (len(MESH_KEYS),))])
+
+
+class SurfaceParams(C.Structure):
+    _fields_ = [("nx", C.c_int64), ("ny", C.c_int64), ("nz", C.c_int64), ("step_size", C.c_int),
+                ("n_labels", C.c_int), ("labels", C.POINTER(C.c_int32))]
+
 
 WALL_BC = {"zero-neumann": 0, "inhomogeneous": 1}  # PTV_WALL_*
 ANCHOR = {"none": 0, "outlet": 1, "inlet": 2}      # PTV_ANCHOR_*
@@ -373,6 +379,12 @@ EXPORTS = {
     "ptv_map_coordinates_dev": (C.c_int, [C.c_void_p, C.POINTER(SplineParams)] + [C.c_void_p] * 4 + [_dp]),
     "ptv_mesh_drag": (C.c_int, [C.c_void_p, C.POINTER(MeshParams)] + [C.c_void_p] * 8 + [_dp]),
     "ptv_mesh_drag_dev": (C.c_int, [C.c_void_p, C.POINTER(MeshParams)] + [C.c_void_p] * 9 + [_dp]),
+    "ptv_abi_sizes11": (C.c_int, [C.POINTER(C.c_int64)]),
+    "ptv_marching_cubes": (C.c_int, [C.c_void_p, C.POINTER(SurfaceParams), C.c_void_p, C.POINTER(C.c_int64),
+                                     C.POINTER(C.c_int64), _dp]),
+    "ptv_marching_cubes_dev": (C.c_int, [C.c_void_p, C.POINTER(SurfaceParams), C.c_void_p, C.c_void_p,
+                                         C.POINTER(C.c_int64), C.POINTER(C.c_int64), _dp]),
+    "ptv_surface_fetch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "ptv_last_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     "ptv_debug_stamps": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double)]),
 }
@@ -510,6 +522,13 @@ def abi_sizes10():
     out = (C.c_int64 * 3)()
     check(lib().ptv_abi_sizes10(out))
     return list(out), [C.sizeof(SplineParams), C.sizeof(MeshParams), C.sizeof(MeshRecord)]
+
+
+def abi_sizes11():
+    """(C sizeof, ctypes sizeof) of ptv_surface_params."""
+    out = (C.c_int64 * 1)()
+    check(lib().ptv_abi_sizes11(out))
+    return list(out), [C.sizeof(SurfaceParams)]
 
 
 def edt_check_shape(shape):
@@ -1470,27 +1489,37 @@ class Context:
         return ms.value
 
     def _mesh_call(self, fn, shape, ptrs, tri_offsets, n_verts, field_dtype, vert_dtype, viscosity, dx, dy, dz, reuse,
-                   extra=()):
-        off = np.ascontiguousarray(tri_offsets, dtype=np.int64).reshape(-1)
+                   extra=(), resident_labels=None):
         nz, ny, nx = shape
-        prm = MeshParams(nx, ny, nz, int(field_dtype), int(vert_dtype), int(n_verts), int(off[-1]), int(off.size - 1),
-                         float(dx), float(dy), float(dz), float(viscosity), int(bool(reuse)),
-                         off.ctypes.data_as(C.POINTER(C.c_int64)))
-        rec = np.zeros(off.size - 1, dtype=MESH_RECORD)
+        if resident_labels is None:
+            off = np.ascontiguousarray(tri_offsets, dtype=np.int64).reshape(-1)
+            prm = MeshParams(nx, ny, nz, int(field_dtype), int(vert_dtype), int(n_verts), int(off[-1]),
+                             int(off.size - 1), float(dx), float(dy), float(dz), float(viscosity), int(bool(reuse)),
+                             off.ctypes.data_as(C.POINTER(C.c_int64)), 0)
+            rec = np.zeros(off.size - 1, dtype=MESH_RECORD)
+        else:  # the context's mesh: the library fills in the counts and the offsets
+            prm = MeshParams(nx, ny, nz, int(field_dtype), F32, 0, 0, int(resident_labels), float(dx), float(dy), float(dz),
+                             float(viscosity), int(bool(reuse)), None, 1)
+            rec = np.zeros(int(resident_labels), dtype=MESH_RECORD)
         ms = (C.c_double * 2)()
         check(fn(self.h, C.byref(prm), *[C.c_void_p(p) if p else None for p in ptrs], *extra,
                  rec.ctypes.data_as(C.c_void_p), ms))
         return rec, {"ms_prefilter": ms[0], "ms_traction": ms[1]}
 
-    def mesh_drag(self, fields, pressure, background, verts, faces, tri_offsets, viscosity, dx, dy, dz, shape=None):
+    def mesh_drag(self, fields, pressure, background, verts, faces, tri_offsets, viscosity, dx, dy, dz, shape=None,
+                  resident_labels=None):
         """Mesh interface drag of host arrays.  ``fields``: u, v, w of one float32 / float64 dtype,
         (nz, ny, nx); ``pressure`` (the same dtype) and ``background`` (uint8 / bool, nonzero = pore
         space) may be None.  ``verts`` (n, 3) float32 / float64 rows z, y, x, ``faces`` (m, 3) indices
         into them, ``tri_offsets`` (labels + 1,): label l owns faces [tri_offsets[l],
         tri_offsets[l + 1]).  ``fields`` None (with ``shape``): the fields, their coefficients, the
         pressure and the background of the previous call stay as they are in the context (no upload,
-        no prefilter).  Returns ``(records, times)``: MESH_RECORD per label, and the prefilters' and
-        the traction kernels' ms."""
+        no prefilter).  ``resident_labels`` (the label count of the context's last ``marching_cubes``):
+        that call's mesh is integrated where it lies on the device; ``verts``, ``faces`` and
+        ``tri_offsets`` are not read and one record per label of that call comes back.  Returns
+        ``(records, times)``: MESH_RECORD per label, and the prefilters' and the traction kernels' ms."""
+        if resident_labels is not None:
+            verts, faces = np.zeros((0, 3), np.float32), np.zeros((0, 3), np.int32)
         vt = np.ascontiguousarray(verts)
         if vt.dtype not in (np.float32, np.float64):
             vt = vt.astype(np.float64)
@@ -1521,9 +1550,46 @@ class Context:
             keep.append(f)
         res = self._mesh_call(lib().ptv_mesh_drag, shape, ptrs + [vt.ctypes.data, fc.ctypes.data], tri_offsets,
                               vt.shape[0], ft, F32 if vt.dtype == np.float32 else F64, viscosity, dx, dy, dz,
-                              reuse=fields is None)
+                              reuse=fields is None, resident_labels=resident_labels)
         self._mesh_dtype = ft
         return res
+
+    # -- marching cubes of a label mask (the triangulation in front of the mesh drag) ----
+    def _surface_call(self, fn, shape, mask_ptr, table, step_size, extra=()):
+        tab = np.ascontiguousarray(table, dtype=np.int32).reshape(-1)
+        nz, ny, nx = (int(n) for n in shape)
+        prm = SurfaceParams(nx, ny, nz, int(step_size), tab.size, tab.ctypes.data_as(C.POINTER(C.c_int32)))
+        nv, nt = np.zeros(tab.size, dtype=np.int64), np.zeros(tab.size, dtype=np.int64)
+        ms = (C.c_double * 2)()
+        check(fn(self.h, C.byref(prm), C.c_void_p(mask_ptr), *extra, nv.ctypes.data_as(C.POINTER(C.c_int64)),
+                 nt.ctypes.data_as(C.POINTER(C.c_int64)), ms))
+        return nv, nt, {"ms_count": ms[0], "ms_emit": ms[1]}
+
+    def marching_cubes(self, mask, table, step_size=1):
+        """Marching cubes of a host int32 (nz, ny, nx) mask for the ascending, distinct, positive int32
+        labels of ``table`` (drag_label_table's), all in one pass.  The mesh stays in the context
+        (``surface_fetch`` copies it out, ``mesh_drag(..., resident_labels=len(table))`` integrates it in
+        place).  Returns ``(vert_counts, tri_counts, times)`` per label of the table."""
+        mk = np.ascontiguousarray(mask, dtype=np.int32)
+        if mk.ndim != 3:
+            raise ValueError(f"a 3-D mask, got {mk.ndim}-D")
+        return self._surface_call(lib().ptv_marching_cubes, mk.shape, mk.ctypes.data, table, step_size)
+
+    def marching_cubes_dev(self, nx, ny, nz, mask_ptr, table, step_size=1, stream=0):
+        """The same for an int32 mask resident in HBM (device pointer)."""
+        return self._surface_call(lib().ptv_marching_cubes_dev, (nz, ny, nx), mask_ptr, table, step_size,
+                                  extra=(C.c_void_p(stream or 0),))
+
+    def surface_fetch(self, vert_counts, tri_counts):
+        """The context's mesh as host arrays: ``[(verts float32 (n, 3), faces int32 (m, 3)), ...]``, one
+        pair per label of the last ``marching_cubes`` (whose counts these are); a label's faces index
+        its own vertices."""
+        nv, nt = int(np.sum(vert_counts)), int(np.sum(tri_counts))
+        verts, faces = np.empty((nv, 3), dtype=np.float32), np.empty((nt, 3), dtype=np.int32)
+        check(lib().ptv_surface_fetch(self.h, verts.ctypes.data_as(C.c_void_p), faces.ctypes.data_as(C.c_void_p)))
+        v0 = np.concatenate([[0], np.cumsum(vert_counts)]).astype(np.int64)
+        t0 = np.concatenate([[0], np.cumsum(tri_counts)]).astype(np.int64)
+        return [(verts[v0[l]:v0[l + 1]], faces[t0[l]:t0[l + 1]]) for l in range(len(v0) - 1)]
 
     def mesh_drag_dev(self, nx, ny, nz, ptrs, pressure_ptr, background_ptr, verts_ptr, n_verts, faces_ptr, tri_offsets,
                       viscosity, dx, dy, dz, field_dtype=F64, vert_dtype=F32, reuse=False, stream=0):

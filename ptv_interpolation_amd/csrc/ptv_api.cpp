@@ -139,6 +139,15 @@ int ptv_abi_sizes10(int64_t out3[3]) {
     return PTV_OK;
 }
 
+int ptv_abi_sizes11(int64_t out1[1]) {
+    if (!out1) {
+        set_error("ptv_abi_sizes11: out is NULL");
+        return PTV_E_ARG;
+    }
+    out1[0] = (int64_t)sizeof(ptv_surface_params);
+    return PTV_OK;
+}
+
 const char *ptv_last_error(void) { return g_last_error.c_str(); }
 
 int ptv_device_count(int *out) {

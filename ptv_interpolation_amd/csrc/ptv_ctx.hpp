@@ -16,6 +16,7 @@
 #include "ptv_mesh.hpp"
 #include "ptv_own.hpp"
 #include "ptv_pressure.hpp"
+#include "ptv_surface.hpp"
 #include "ptv_variational.hpp"
 
 namespace ptv {
@@ -133,6 +134,9 @@ struct ptv_ctx {
     ptv::DevBuf<int64_t> mesh_blk_first, mesh_lab_blk0, mesh_off;     // block -> first triangle; per-label tables
     ptv::DevBuf<double> mesh_part, mesh_res;                          // per-block partials, per-label sums
     ptv::Event ev_mesh[3];                                            // prefilter start, traction start, end
+    ptv::SurfWork surf;                                               // marching cubes: scratch, the resident mesh
+    ptv::DevBuf<int32_t> surf_mask;                                   // its host calls: the mask
+    ptv::Event ev_surf[3];                                            // counting start, emission start, end
     ptv::PinnedBuf<double> h_bbox;                                    // pinned, kHostWords doubles
     ptv::PinnedBuf<unsigned long long> h_misc;  // pinned scratch words (cull count, halo bound, repair count)
     ptv_stats last{};

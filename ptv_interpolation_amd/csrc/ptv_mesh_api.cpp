@@ -110,6 +110,32 @@ int mesh_args(ptv_ctx *c, const ptv_mesh_params *prm, MeshArgs &a) {
     return PTV_OK;
 }
 
+// prm->mesh_resident: the parameters with the mesh that the context's last marching cubes left on
+// the device in place of the caller's
+int resident_mesh(ptv_ctx *c, const ptv_mesh_params *prm, ptv_mesh_params &out) {
+    if (!c || !prm) {
+        set_error("NULL context/params");
+        return PTV_E_ARG;
+    }
+    out = *prm;
+    if (!prm->mesh_resident) return PTV_OK;
+    const SurfWork &w = c->surf;
+    if (w.n_labels < 1 || w.tstart[w.n_labels] < 1) {
+        set_error("mesh drag: mesh_resident, but the context holds no mesh with a triangle");
+        return PTV_E_ARG;
+    }
+    if (prm->n_labels != w.n_labels) {  // the caller's records have room for n_labels
+        set_error("mesh drag: mesh_resident, but n_labels is not the label count of the context's mesh");
+        return PTV_E_ARG;
+    }
+    out.vert_dtype = PTV_F32;
+    out.n_verts = w.vstart[w.n_labels];
+    out.n_tris = w.tstart[w.n_labels];
+    out.n_labels = w.n_labels;
+    out.tri_offsets = w.tstart.data();
+    return PTV_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -211,9 +237,16 @@ int ptv_map_coordinates(ptv_ctx *c, const ptv_spline_params *prm, const void *fi
     return PTV_OK;
 }
 
-int ptv_mesh_drag_dev(ptv_ctx *c, const ptv_mesh_params *prm, const void *U, const void *V, const void *W,
+int ptv_mesh_drag_dev(ptv_ctx *c, const ptv_mesh_params *given, const void *U, const void *V, const void *W,
                       const void *P, const uint8_t *bg, const void *verts, const int32_t *faces, void *stream,
                       ptv_mesh_record *records, double ms2[2]) {
+    ptv_mesh_params resolved;
+    PTV_TRY(resident_mesh(c, given, resolved));
+    const ptv_mesh_params *prm = &resolved;
+    if (prm->mesh_resident) {
+        verts = c->surf.verts.p;
+        faces = c->surf.faces.p;
+    }
     MeshArgs a{};
     PTV_TRY(mesh_args(c, prm, a));
     if (!U || !V || !W || !verts || !faces || !records) {
@@ -281,12 +314,16 @@ int ptv_mesh_drag_dev(ptv_ctx *c, const ptv_mesh_params *prm, const void *U, con
     return PTV_OK;
 }
 
-int ptv_mesh_drag(ptv_ctx *c, const ptv_mesh_params *prm, const void *U, const void *V, const void *W, const void *P,
+int ptv_mesh_drag(ptv_ctx *c, const ptv_mesh_params *given, const void *U, const void *V, const void *W, const void *P,
                   const uint8_t *bg, const void *verts, const int32_t *faces, ptv_mesh_record *records,
                   double ms2[2]) {
+    ptv_mesh_params resolved;
+    PTV_TRY(resident_mesh(c, given, resolved));
+    const ptv_mesh_params *prm = &resolved;
+    const bool resident = prm->mesh_resident != 0;
     MeshArgs a{};
     PTV_TRY(mesh_args(c, prm, a));
-    if (!verts || !faces || !records || (!prm->reuse && (!U || !V || !W))) {
+    if ((!resident && (!verts || !faces)) || !records || (!prm->reuse && (!U || !V || !W))) {
         set_error("mesh drag: NULL field, vertices, faces or records");
         return PTV_E_ARG;
     }
@@ -294,7 +331,7 @@ int ptv_mesh_drag(ptv_ctx *c, const ptv_mesh_params *prm, const void *U, const v
         set_error("mesh drag: reuse, but the context holds no fields of these dimensions and dtype");
         return PTV_E_ARG;
     }
-    for (int64_t i = 0; i < 3 * prm->n_tris; ++i)
+    for (int64_t i = 0; !resident && i < 3 * prm->n_tris; ++i)
         if (faces[i] < 0 || faces[i] >= prm->n_verts) {
             set_error("mesh drag: a face index lies outside [0, n_verts)");
             return PTV_E_ARG;
@@ -316,14 +353,18 @@ int ptv_mesh_drag(ptv_ctx *c, const ptv_mesh_params *prm, const void *U, const v
         c->mesh_has_p = P != nullptr;
         c->mesh_has_bg = bg != nullptr;
     }
-    const size_t vbytes = (size_t)prm->n_verts * 3 * (a.vert_f32 ? 4 : 8);
-    PTV_TRY(c->mesh_verts.ensure(vbytes));
-    PTV_TRY(c->mesh_faces.ensure((size_t)prm->n_tris * 3));
-    PTV_HIP(hipMemcpyAsync(c->mesh_verts.p, verts, vbytes, hipMemcpyHostToDevice, s));
-    PTV_HIP(hipMemcpyAsync(c->mesh_faces.p, faces, (size_t)prm->n_tris * 3 * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    PTV_TRY(ptv_mesh_drag_dev(c, prm, c->mesh_fld[0].p, c->mesh_fld[1].p, c->mesh_fld[2].p,
+    if (!resident) {  // a resident mesh is integrated where the marching cubes left it
+        const size_t vbytes = (size_t)prm->n_verts * 3 * (a.vert_f32 ? 4 : 8);
+        PTV_TRY(c->mesh_verts.ensure(vbytes));
+        PTV_TRY(c->mesh_faces.ensure((size_t)prm->n_tris * 3));
+        PTV_HIP(hipMemcpyAsync(c->mesh_verts.p, verts, vbytes, hipMemcpyHostToDevice, s));
+        PTV_HIP(hipMemcpyAsync(c->mesh_faces.p, faces, (size_t)prm->n_tris * 3 * sizeof(int32_t),
+                               hipMemcpyHostToDevice, s));
+    }
+    PTV_TRY(ptv_mesh_drag_dev(c, given, c->mesh_fld[0].p, c->mesh_fld[1].p, c->mesh_fld[2].p,
                               c->mesh_has_p ? c->mesh_fld[3].p : nullptr, c->mesh_has_bg ? c->mesh_bg.p : nullptr,
-                              c->mesh_verts.p, c->mesh_faces.p, s, records, ms2));
+                              resident ? nullptr : c->mesh_verts.p, resident ? nullptr : c->mesh_faces.p, s, records,
+                              ms2));
     c->mesh_fld_dtype = prm->field_dtype;
     return PTV_OK;
 }

@@ -30,6 +30,11 @@ fallback), everything from the mesh onward runs on the GPU.  ``method='mesh'`` t
 through the reference's own dispatch, and with ``PTV_GPU_DRAG=1`` through the forwarding above.
 ``integrate_mesh_drag`` (the integration for meshes from any source) is always provided.
 
+With ``PTV_GPU_MARCHING_CUBES=1`` as well, the function installed for ``compute_interface_drag_mesh``
+calls the GPU one with ``triangulation='device'``: marching cubes runs on the GPU too and scikit-image
+is not needed.  Its triangles are those of this project's own rule, not scikit-image's (DESIGN.md
+section 23).  The variable has no effect without ``PTV_GPU_DRAG_MESH=1``.
+
 Without the reference module (the GPU box), the five functions, ``analyze``, the two drag functions
 above, ``compute_interface_drag_mesh``, ``compute_pressure_field``, ``recover_pressure`` and
 ``compute_force_field`` are provided.
@@ -95,13 +100,23 @@ def _drag_with_host_mesh(mesh):
     return compute_interface_drag
 
 
+def _mesh_on_device():
+    """The GPU mesh drag with the reference's signature and the triangulation on the device too."""
+    def compute_interface_drag_mesh(u, v, w, pressure, viscosity, dx, dy, dz, mask, labels=None, mesh_step=1, volume=None, background_mask=None):
+        return _gpu.compute_interface_drag_mesh(u, v, w, pressure, viscosity, dx, dy, dz, mask, labels, mesh_step,
+                                                volume, background_mask, triangulation='device')
+    compute_interface_drag_mesh.__doc__ = _gpu.compute_interface_drag_mesh.__doc__
+    return compute_interface_drag_mesh
+
+
 integrate_mesh_drag = _gpu.integrate_mesh_drag
 # before the staircase opt-in, whose method='mesh' forwards to whatever the module holds by then
 if _ref is None:
     compute_interface_drag_mesh = _gpu.compute_interface_drag_mesh
 elif _os.environ.get("PTV_GPU_DRAG_MESH") == "1":
-    compute_interface_drag_mesh = _gpu.compute_interface_drag_mesh
-    _ref.compute_interface_drag_mesh = _gpu.compute_interface_drag_mesh
+    compute_interface_drag_mesh = (_mesh_on_device() if _os.environ.get("PTV_GPU_MARCHING_CUBES") == "1"
+                                   else _gpu.compute_interface_drag_mesh)
+    _ref.compute_interface_drag_mesh = compute_interface_drag_mesh
 
 if _ref is None:
     for _n in _DRAG_NAMES:
