@@ -591,6 +591,33 @@ typedef struct {
     const int32_t *labels; /* n_labels ascending, distinct, positive; HOST memory in both calls */
 } ptv_surface_params;
 
+/*
+ * Connected-component labelling of a byte mask: scipy.ndimage.label for 3-D inputs, bit for bit.  The
+ * mask is uint8 (nz, ny, nx) C order, nonzero = foreground.  Two foreground voxels are neighbours when
+ * their offset has at most 1, 2 or 3 nonzero components (each +-1): connectivity 6, 18 or 26, scipy's
+ * generate_binary_structure(3, 1 / 2 / 3).  labels is int32 of the mask's shape: 0 at background, and
+ * the components numbered from 1 in the raster order (z slowest, x fastest) of their first voxels,
+ * which is scipy's numbering.  The output is the same bytes on every call.
+ * sizes (may be NULL) receives n_components + 1 voxel counts, the background's at index 0, i.e.
+ * np.bincount(labels); the count is not known before the call, so the buffer must have room for
+ * (nx * ny * nz + 1) / 2 + 1 entries, which no mask exceeds.  The voxel count must stay below 2^31
+ * (PTV_E_UNSUPPORTED); a connectivity other than 6, 18, 26, a NULL pointer or a non-positive extent is
+ * PTV_E_ARG; all are decided before any device work.  The call synchronises twice: for the component
+ * count (it sizes `sizes`) and at the end.
+ * PTV_API_VERSION is not raised: the presence of ptv_abi_sizes12 is the capability probe.
+ */
+typedef struct {
+    int64_t nz, ny, nx;  /* positive */
+    int connectivity;    /* 6, 18 or 26 */
+} ptv_label_params;
+
+typedef struct {
+    int64_t n_components;
+    int64_t n_foreground; /* nonzero voxels of the mask */
+    double ms_merge;      /* tile-local labelling and border merge, hipEvent based */
+    double ms_number;     /* flatten, scan and numbering (with the sizes) */
+} ptv_label_stats;
+
 /* Library / device management. */
 int ptv_version(void);
 /* sizeof(ptv_particles, ptv_grid, ptv_knn_params, ptv_stats, ptv_rbf_params, ptv_div_params):
@@ -624,6 +651,9 @@ int ptv_abi_sizes10(int64_t out3[3]);
 /* sizeof(ptv_surface_params): the same self-check.  A library that has this symbol has the marching
  * cubes entry points and ptv_mesh_params.mesh_resident (PTV_API_VERSION stays 11). */
 int ptv_abi_sizes11(int64_t out1[1]);
+/* sizeof(ptv_label_params, ptv_label_stats): the same self-check.  A library that has this symbol has
+ * the component labelling entry points (PTV_API_VERSION stays 11). */
+int ptv_abi_sizes12(int64_t out2[2]);
 const char *ptv_last_error(void);
 int ptv_device_count(int *out);
 int ptv_init(int device, ptv_ctx **out);
@@ -1001,6 +1031,19 @@ int ptv_marching_cubes_dev(ptv_ctx *ctx, const ptv_surface_params *prm, const in
  * int32 (host), label after label; a label's faces index its own vertices.  Either may be NULL.
  * PTV_E_ARG when the context holds no mesh. */
 int ptv_surface_fetch(ptv_ctx *ctx, float *verts, int32_t *faces);
+
+/*
+ * Component labelling, host buffers: H2D of the mask, the four passes, D2H of the labels and, when
+ * sizes is not NULL, of its first n_components + 1 entries.  st may be NULL.
+ */
+int ptv_label(ptv_ctx *ctx, const ptv_label_params *prm, const uint8_t *mask, int32_t *labels, int64_t *sizes,
+              ptv_label_stats *st);
+
+/* Same on device pointers (mask, labels, sizes), enqueued on `stream` (NULL = the ctx's own);
+ * synchronises (the counts are returned).  The labels stay on the device, where ptv_interface_drag_dev
+ * and ptv_marching_cubes_dev take them as their int32 mask. */
+int ptv_label_dev(ptv_ctx *ctx, const ptv_label_params *prm, const uint8_t *mask, int32_t *labels, int64_t *sizes,
+                  void *stream, ptv_label_stats *st);
 
 /*
  * Last-launch k-NN kernel duration in ms (hipEvent pair recorded around the

@@ -211,6 +211,15 @@ class SurfaceParams(C.Structure):
                 ("n_labels", C.c_int), ("labels", C.POINTER(C.c_int32))]
 
 
+class LabelParams(C.Structure):
+    _fields_ = [("nz", C.c_int64), ("ny", C.c_int64), ("nx", C.c_int64), ("connectivity", C.c_int)]
+
+
+class LabelStats(C.Structure):
+    _fields_ = [("n_components", C.c_int64), ("n_foreground", C.c_int64), ("ms_merge", C.c_double),
+                ("ms_number", C.c_double)]
+
+
 WALL_BC = {"zero-neumann": 0, "inhomogeneous": 1}  # PTV_WALL_*
 ANCHOR = {"none": 0, "outlet": 1, "inlet": 2}      # PTV_ANCHOR_*
 FLOW_DIRECTION = {"auto": 0, "positive": 1, "negative": -1}
@@ -385,6 +394,9 @@ EXPORTS = {
     "ptv_marching_cubes_dev": (C.c_int, [C.c_void_p, C.POINTER(SurfaceParams), C.c_void_p, C.c_void_p,
                                          C.POINTER(C.c_int64), C.POINTER(C.c_int64), _dp]),
     "ptv_surface_fetch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ptv_abi_sizes12": (C.c_int, [C.POINTER(C.c_int64)]),
+    "ptv_label": (C.c_int, [C.c_void_p, C.POINTER(LabelParams)] + [C.c_void_p] * 3 + [C.POINTER(LabelStats)]),
+    "ptv_label_dev": (C.c_int, [C.c_void_p, C.POINTER(LabelParams)] + [C.c_void_p] * 4 + [C.POINTER(LabelStats)]),
     "ptv_last_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     "ptv_debug_stamps": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double)]),
 }
@@ -529,6 +541,30 @@ def abi_sizes11():
     out = (C.c_int64 * 1)()
     check(lib().ptv_abi_sizes11(out))
     return list(out), [C.sizeof(SurfaceParams)]
+
+
+def abi_sizes12():
+    """(C sizeof, ctypes sizeof) of ptv_label_params and ptv_label_stats."""
+    out = (C.c_int64 * 2)()
+    check(lib().ptv_abi_sizes12(out))
+    return list(out), [C.sizeof(LabelParams), C.sizeof(LabelStats)]
+
+
+def label_check_shape(shape):
+    """The (nz, ny, nx) the labelling takes: 3-D and fewer than 2^31 voxels (``NotImplementedError``
+    otherwise).  Looks at the shape alone."""
+    if len(shape) != 3:
+        raise NotImplementedError(f"the GPU labelling is 3-D only (got {len(shape)}-D)")
+    shape = tuple(int(n) for n in shape)
+    if shape[0] * shape[1] * shape[2] >= 2**31:
+        raise NotImplementedError(f"shape {shape}: 2^31 or more voxels (voxel indices are 32-bit on the GPU)")
+    return shape
+
+
+def label_sizes_room(n_voxels):
+    """Entries a ``sizes`` buffer needs before the component count is known: no mask of ``n_voxels``
+    has more than ceil(n / 2) components (the 6-neighbour checkerboard), plus the background."""
+    return (int(n_voxels) + 1) // 2 + 1
 
 
 def edt_check_shape(shape):
@@ -1590,6 +1626,41 @@ class Context:
         v0 = np.concatenate([[0], np.cumsum(vert_counts)]).astype(np.int64)
         t0 = np.concatenate([[0], np.cumsum(tri_counts)]).astype(np.int64)
         return [(verts[v0[l]:v0[l + 1]], faces[t0[l]:t0[l + 1]]) for l in range(len(v0) - 1)]
+
+    # -- connected-component labelling (scipy.ndimage.label) ----
+    @staticmethod
+    def _label_stats(st):
+        return {"n_components": int(st.n_components), "n_foreground": int(st.n_foreground),
+                "ms_merge": st.ms_merge, "ms_number": st.ms_number}
+
+    def label(self, mask, connectivity=6, want_sizes=False):
+        """Labels the components of a host uint8 (nz, ny, nx) ``mask`` (nonzero = foreground) under 6, 18
+        or 26 neighbours, numbered as scipy.ndimage.label numbers them.  Returns ``(labels, sizes,
+        stats)``: int32 labels, the int64 voxel counts per label with the background first (None
+        unless ``want_sizes``) and ``{"n_components", "n_foreground", "ms_merge", "ms_number"}``."""
+        nz, ny, nx = label_check_shape(mask.shape)
+        mk = np.ascontiguousarray(mask, dtype=np.uint8)
+        labels = np.empty(mk.shape, dtype=np.int32)
+        sizes = np.empty(label_sizes_room(mk.size), dtype=np.int64) if want_sizes else None
+        prm = LabelParams(nz, ny, nx, int(connectivity))
+        st = LabelStats()
+        check(lib().ptv_label(self.h, C.byref(prm), mk.ctypes.data_as(C.c_void_p), labels.ctypes.data_as(C.c_void_p),
+                              sizes.ctypes.data_as(C.c_void_p) if want_sizes else None, C.byref(st)))
+        if want_sizes:
+            sizes = sizes[:int(st.n_components) + 1].copy()
+        return labels, sizes, self._label_stats(st)
+
+    def label_dev(self, nx, ny, nz, mask_ptr, labels_ptr, connectivity=6, sizes_ptr=0, stream=0):
+        """The same for a uint8 mask resident in HBM: ``labels_ptr`` (int32, the mask's shape) and
+        ``sizes_ptr`` (int64, ``label_sizes_room(n)`` entries, 0 = not wanted) are device pointers.  The
+        labels stay on the device.  Returns the stats."""
+        label_check_shape((nz, ny, nx))
+        prm = LabelParams(nz, ny, nx, int(connectivity))
+        st = LabelStats()
+        check(lib().ptv_label_dev(self.h, C.byref(prm), C.c_void_p(mask_ptr), C.c_void_p(labels_ptr),
+                                  C.c_void_p(sizes_ptr) if sizes_ptr else None, C.c_void_p(stream or 0),
+                                  C.byref(st)))
+        return self._label_stats(st)
 
     def mesh_drag_dev(self, nx, ny, nz, ptrs, pressure_ptr, background_ptr, verts_ptr, n_verts, faces_ptr, tri_offsets,
                       viscosity, dx, dy, dz, field_dtype=F64, vert_dtype=F32, reuse=False, stream=0):

@@ -22,7 +22,7 @@ BUILD = os.path.join(HERE, "csrc", "_build")
 # the k-NN kernel's list lengths compile in parallel (ptv_knn_k*.hip instantiate ptv_knn_impl.hpp)
 KNN_PARTS = ["ptv_knn_k" + g + ".hip" for g in "abcdefgh"]
 SOURCES = (["ptv_api.cpp", "ptv_search.cpp", "ptv_run_knn.cpp", "ptv_run_chunked.cpp", "ptv_mesh_api.cpp", "ptv_mesh.hip",
-            "ptv_surface_api.cpp", "ptv_surface.hip",
+            "ptv_surface_api.cpp", "ptv_surface.hip", "ptv_label_api.cpp", "ptv_label.hip",
             "ptv_bin.hip", "ptv_knn.hip"] + KNN_PARTS +
            ["ptv_rbf.hip"] + ["ptv_rbf_ns_" + g + ".hip" for g in "abcd"] +
            ["ptv_div.hip", "ptv_flow.hip", "ptv_drag.hip", "ptv_edt.hip", "ptv_clean.hip", "ptv_variational.hip", "ptv_pressure.hip", "ptv_mask.hip", "ptv_filter.hip", "ptv_linear.hip", "ptv_knn_big.hip"])

@@ -13,6 +13,7 @@
 #include "ptv_clean.hpp"
 #include "ptv_kernels.hpp"
 #include "ptv_knn_big.hpp"
+#include "ptv_label.hpp"
 #include "ptv_mesh.hpp"
 #include "ptv_own.hpp"
 #include "ptv_pressure.hpp"
@@ -137,6 +138,10 @@ struct ptv_ctx {
     ptv::SurfWork surf;                                               // marching cubes: scratch, the resident mesh
     ptv::DevBuf<int32_t> surf_mask;                                   // its host calls: the mask
     ptv::Event ev_surf[3];                                            // counting start, emission start, end
+    ptv::LabelWork label;                                             // component labelling: forest, flags, ranks
+    ptv::DevBuf<uint8_t> label_mask;                                  // its host calls: the mask
+    ptv::DevBuf<int32_t> label_out;                                   //   and the labels
+    ptv::Event ev_label[3];                                           // start, after the border merge, end
     ptv::PinnedBuf<double> h_bbox;                                    // pinned, kHostWords doubles
     ptv::PinnedBuf<unsigned long long> h_misc;  // pinned scratch words (cull count, halo bound, repair count)
     ptv_stats last{};
