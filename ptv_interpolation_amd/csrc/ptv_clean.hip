@@ -25,28 +25,20 @@
 //
 // Reductions are two-stage and fixed-order (wave64 DPP sum, LDS across the block's 4 waves, then
 // the one-block kernel over the partials): no floating-point atomics, so a call repeats bit for bit.
-// Every kernel returns at once when the state's stop flag is set; the host polls the state once
-// per kPoll iterations, one batch behind the enqueue, so x and itn are those of the iteration whose
-// tests stopped the solve.
+// The stop flag, the polling loop and the event numbering are those of ptv_grid_solve.hpp.
 #include <cmath>
 #include <algorithm>
 
 #include "ptv_clean.hpp"
-#include "ptv_grid_vec.hpp"
-#include "ptv_kernels.hpp"
+#include "ptv_grid_solve.hpp"
 
 namespace ptv {
 
 namespace {
 
-constexpr int kThreads = kGridThreads;
-constexpr int kItems = kGridItems;
-constexpr int kPoll = 8;    // LSQR iterations between two polls of the stop flag
-constexpr int kFinalThreads = kGridFinalThreads;
-
 // device-resident LSQR state (doubles; names follow scipy's lsqr)
 enum {
-    S_STOP = 0, S_ISTOP, S_ITN, S_ALFA, S_BETA, S_INV_ALFA, S_INV_BETA, S_RHOBAR, S_PHIBAR, S_ANORM,
+    S_STOP = kStopSlot, S_ISTOP, S_ITN, S_ALFA, S_BETA, S_INV_ALFA, S_INV_BETA, S_RHOBAR, S_PHIBAR, S_ANORM,
     S_DDNORM, S_RES2, S_XNORM, S_XXNORM, S_Z, S_CS2, S_SN2, S_BNORM, S_RNORM, S_ARNORM, S_ACOND, S_T1,
     S_T2, S_INV_RHO, S_SKIPV, S_MEAN, S_MEANABS, S_NFLUID, S_NAN, S_COUNT
 };
@@ -109,10 +101,10 @@ __device__ __forceinline__ DV<VEC> lap_group(const CleanArgs &a, const double *_
 
 // y = A x (ptv_laplacian_apply): solid voxels are written as 0
 template <int VEC>
-__global__ __launch_bounds__(kThreads) void k_laplacian(CleanArgs a, const double *__restrict__ X,
+__global__ __launch_bounds__(kGridThreads) void k_laplacian(CleanArgs a, const double *__restrict__ X,
                                                         const uint8_t *__restrict__ M, double *__restrict__ Y) {
 #pragma unroll
-    for (int it = 0; it < kItems; ++it) {
+    for (int it = 0; it < kGridItems; ++it) {
         Pos p;
         if (!group_pos<VEC>(a, it, p)) break;
         const MV<VEC> mc = ldmk<VEC>(M + p.i);
@@ -123,7 +115,7 @@ __global__ __launch_bounds__(kThreads) void k_laplacian(CleanArgs a, const doubl
 // Golub-Kahan step: Y <- A (sx X) - c (sy Y) on fluid voxels, partial sums of the new Y^2.
 // which = 0: u <- A v - alfa u (lsqr.py:430);  which = 1: v <- A^T u - beta v (:436)
 template <int VEC>
-__global__ __launch_bounds__(kThreads) void k_bidiag(CleanArgs a, int which, const double *__restrict__ st,
+__global__ __launch_bounds__(kGridThreads) void k_bidiag(CleanArgs a, int which, const double *__restrict__ st,
                                                      const double *__restrict__ X, double *__restrict__ Y,
                                                      const uint8_t *__restrict__ M, double *__restrict__ part) {
     if (st[S_STOP] != 0.0) return;
@@ -133,7 +125,7 @@ __global__ __launch_bounds__(kThreads) void k_bidiag(CleanArgs a, int which, con
     const double c = which == 0 ? st[S_ALFA] : st[S_BETA];
     double ss = 0.0;
 #pragma unroll
-    for (int it = 0; it < kItems; ++it) {
+    for (int it = 0; it < kGridItems; ++it) {
         Pos p;
         if (!group_pos<VEC>(a, it, p)) break;
         const MV<VEC> mc = ldmk<VEC>(M + p.i);
@@ -157,7 +149,7 @@ __global__ __launch_bounds__(kThreads) void k_bidiag(CleanArgs a, int which, con
 
 // x <- x + t1 w;  w <- v + t2 w;  partial sums of ((1/rho) w)^2 (lsqr.py:465-471)
 template <int VEC>
-__global__ __launch_bounds__(kThreads) void k_update(CleanArgs a, const double *__restrict__ st,
+__global__ __launch_bounds__(kGridThreads) void k_update(CleanArgs a, const double *__restrict__ st,
                                                      const double *__restrict__ V, double *__restrict__ W,
                                                      double *__restrict__ Xs, const uint8_t *__restrict__ M,
                                                      double *__restrict__ part) {
@@ -165,7 +157,7 @@ __global__ __launch_bounds__(kThreads) void k_update(CleanArgs a, const double *
     const double t1 = st[S_T1], t2 = st[S_T2], ir = st[S_INV_RHO], ia = st[S_INV_ALFA];
     double ss = 0.0;
 #pragma unroll
-    for (int it = 0; it < kItems; ++it) {
+    for (int it = 0; it < kGridItems; ++it) {
         Pos p;
         if (!group_pos<VEC>(a, it, p)) break;
         const MV<VEC> mc = ldmk<VEC>(M + p.i);
@@ -192,13 +184,13 @@ __global__ __launch_bounds__(kThreads) void k_update(CleanArgs a, const double *
 
 // LSQR's first u: b = div[fluid] - mean(div[fluid]) (physics.py:182-183), partial sums of b^2
 template <int VEC>
-__global__ __launch_bounds__(kThreads) void k_rhs(CleanArgs a, const double *__restrict__ st,
+__global__ __launch_bounds__(kGridThreads) void k_rhs(CleanArgs a, const double *__restrict__ st,
                                                   const double *__restrict__ D, const uint8_t *__restrict__ M,
                                                   double *__restrict__ U, double *__restrict__ part) {
     const double mean = st[S_MEAN];
     double ss = 0.0;
 #pragma unroll
-    for (int it = 0; it < kItems; ++it) {
+    for (int it = 0; it < kGridItems; ++it) {
         Pos p;
         if (!group_pos<VEC>(a, it, p)) break;
         const MV<VEC> mc = ldmk<VEC>(M + p.i);
@@ -217,11 +209,11 @@ __global__ __launch_bounds__(kThreads) void k_rhs(CleanArgs a, const double *__r
 
 // partial counts of NaN entries of the solution
 template <int VEC>
-__global__ __launch_bounds__(kThreads) void k_nan(CleanArgs a, const double *__restrict__ Xs,
+__global__ __launch_bounds__(kGridThreads) void k_nan(CleanArgs a, const double *__restrict__ Xs,
                                                   double *__restrict__ part) {
     double c = 0.0;
 #pragma unroll
-    for (int it = 0; it < kItems; ++it) {
+    for (int it = 0; it < kGridItems; ++it) {
         Pos p;
         if (!group_pos<VEC>(a, it, p)) break;
         const DV<VEC> x = ldd<VEC>(Xs + p.i);
@@ -233,12 +225,12 @@ __global__ __launch_bounds__(kThreads) void k_nan(CleanArgs a, const double *__r
 }
 
 // net x-flux through the middle YZ plane: sum(u[:, :, nx // 2]) * dy * dz (physics.py:160-165)
-__global__ __launch_bounds__(kFinalThreads) void k_flux(CleanArgs a, const double *__restrict__ U,
+__global__ __launch_bounds__(kGridFinalThreads) void k_flux(CleanArgs a, const double *__restrict__ U,
                                                         double *__restrict__ rep, int slot) {
     const unsigned rows = (unsigned)a.ny * (unsigned)a.nz;
     const unsigned mid = (unsigned)(a.nx / 2);
     double s = 0.0;
-    for (unsigned r = threadIdx.x; r < rows; r += kFinalThreads) s += U[r * (unsigned)a.nx + mid];
+    for (unsigned r = threadIdx.x; r < rows; r += kGridFinalThreads) s += U[r * (unsigned)a.nx + mid];
     s = block_sum(s);
     if (threadIdx.x == 0) rep[slot] = s * a.dy * a.dz;
 }
@@ -268,24 +260,19 @@ __device__ __forceinline__ void sym_ortho(double a, double b, double &c, double 
     }
 }
 
-// Second reduction stage and the scalar recurrences.  One block: the partials are summed in a fixed
-// order (thread t takes entries t, t + 256, ...; then the block sum), then thread 0 alone advances
-// the state exactly as scipy's lsqr does between its vector operations.
-__global__ __launch_bounds__(kFinalThreads) void k_scalar(int phase, LsqrCfg cfg, double *__restrict__ st,
+// Second reduction stage and the scalar recurrences.  One block sums the partials in a fixed order
+// (partial_sum), then thread 0 alone advances the state exactly as scipy's lsqr does between its
+// vector operations.
+__global__ __launch_bounds__(kGridFinalThreads) void k_scalar(int phase, LsqrCfg cfg, double *__restrict__ st,
                                                           const double *__restrict__ part, unsigned npart,
                                                           double *__restrict__ rep, int slot) {
     const bool solver = phase == PH_BETA || phase == PH_ALFA || phase == PH_TEST;
     if (solver && st[S_STOP] != 0.0) return;
-    double r0 = 0.0, r1 = 0.0, r2 = 0.0;
-    for (unsigned k = threadIdx.x; k < npart; k += kFinalThreads) r0 += part[k];
-    r0 = block_sum(r0);
+    const double r0 = partial_sum(part, npart);
+    double r1 = 0.0, r2 = 0.0;
     if (phase == PH_DIVSTATS) {
-        for (unsigned k = threadIdx.x; k < npart; k += kFinalThreads) {
-            r1 += part[npart + k];
-            r2 += part[2 * npart + k];
-        }
-        r1 = block_sum(r1);
-        r2 = block_sum(r2);
+        r1 = partial_sum(part + npart, npart);
+        r2 = partial_sum(part + 2 * npart, npart);
     }
     if (threadIdx.x != 0) return;
     const double dampsq = cfg.damp * cfg.damp;
@@ -427,12 +414,12 @@ __global__ __launch_bounds__(kFinalThreads) void k_scalar(int phase, LsqrCfg cfg
 // in the reference's operation order: bit-identical to numpy given the same phi.  May run in place
 // (Uo == U): a voxel reads only its own velocity.
 template <int VEC>
-__global__ __launch_bounds__(kThreads) void k_correction(CleanArgs a, const double *__restrict__ P,
+__global__ __launch_bounds__(kGridThreads) void k_correction(CleanArgs a, const double *__restrict__ P,
                                                          const uint8_t *__restrict__ M, const double *U,
                                                          const double *V, const double *W, double *Uo, double *Vo,
                                                          double *Wo) {
 #pragma unroll
-    for (int it = 0; it < kItems; ++it) {
+    for (int it = 0; it < kGridItems; ++it) {
         Pos p;
         if (!group_pos<VEC>(a, it, p)) break;
         const unsigned i = p.i;
@@ -475,25 +462,12 @@ __global__ __launch_bounds__(kThreads) void k_correction(CleanArgs a, const doub
 }
 
 int make_args(const CleanGrid &g, CleanArgs &a) {
-    if (g.nx <= 0 || g.ny <= 0 || g.nz <= 0) {
-        set_error("clean: dimensions must be positive");
-        return PTV_E_ARG;
-    }
-    const long long n = (long long)g.nx * g.ny * g.nz;
-    if (n > 0x7fff0000LL) {
-        set_error("clean: grids of 2^31 voxels or more are not supported");
-        return PTV_E_ARG;
-    }
+    PTV_TRY(grid_dims("clean", g.nx, g.ny, g.nz, a));
     if (!(g.dx != 0.0) || !(g.dy != 0.0) || !(g.dz != 0.0) || std::isnan(g.dx) || std::isnan(g.dy) ||
         std::isnan(g.dz)) {
         set_error("clean: spacings must be non-zero numbers");
         return PTV_E_ARG;
     }
-    a.nx = g.nx;
-    a.ny = g.ny;
-    a.nz = g.nz;
-    a.n = (unsigned)n;
-    a.plane = (unsigned)g.nx * (unsigned)g.ny;
     a.dx = g.dx;
     a.dy = g.dy;
     a.dz = g.dz;
@@ -516,45 +490,34 @@ struct Solver {
     int bidiag(int which) {
         const double *X = which == 0 ? wk.v.p : wk.u.p;
         double *Y = which == 0 ? wk.u.p : wk.v.p;
-        if (vec2) hipLaunchKernelGGL(k_bidiag<2>, dim3(nb), dim3(kThreads), 0, s, a, which, wk.state.p, X, Y, M, wk.part.p);
-        else hipLaunchKernelGGL(k_bidiag<1>, dim3(nb), dim3(kThreads), 0, s, a, which, wk.state.p, X, Y, M, wk.part.p);
-        PTV_HIP(hipGetLastError());
+        GRID_LAUNCH(k_bidiag, vec2, nb, s, a, which, wk.state.p, X, Y, M, wk.part.p);
         return PTV_OK;
     }
     int update() {
-        if (vec2) hipLaunchKernelGGL(k_update<2>, dim3(nb), dim3(kThreads), 0, s, a, wk.state.p, wk.v.p, wk.w.p, wk.x.p, M, wk.part.p);
-        else hipLaunchKernelGGL(k_update<1>, dim3(nb), dim3(kThreads), 0, s, a, wk.state.p, wk.v.p, wk.w.p, wk.x.p, M, wk.part.p);
-        PTV_HIP(hipGetLastError());
+        GRID_LAUNCH(k_update, vec2, nb, s, a, wk.state.p, wk.v.p, wk.w.p, wk.x.p, M, wk.part.p);
         return PTV_OK;
     }
     int scalar(int phase, int slot = 0) {
-        hipLaunchKernelGGL(k_scalar, dim3(1), dim3(kFinalThreads), 0, s, phase, cfg, wk.state.p, wk.part.p, nb, wk.rep.p, slot);
+        hipLaunchKernelGGL(k_scalar, dim3(1), dim3(kGridFinalThreads), 0, s, phase, cfg, wk.state.p, wk.part.p, nb, wk.rep.p, slot);
         PTV_HIP(hipGetLastError());
         return PTV_OK;
     }
     int div_stats(int slot) {
-        if (vec2) hipLaunchKernelGGL(k_div_stats<2>, dim3(nb), dim3(kThreads), 0, s, a, wk.div.p, M, wk.part.p, nb);
-        else hipLaunchKernelGGL(k_div_stats<1>, dim3(nb), dim3(kThreads), 0, s, a, wk.div.p, M, wk.part.p, nb);
-        PTV_HIP(hipGetLastError());
+        GRID_LAUNCH(k_div_stats, vec2, nb, s, a, wk.div.p, M, wk.part.p, nb);
         return scalar(PH_DIVSTATS, slot);
     }
     int flux(const double *U, int slot) {
-        hipLaunchKernelGGL(k_flux, dim3(1), dim3(kFinalThreads), 0, s, a, U, wk.rep.p, slot);
+        hipLaunchKernelGGL(k_flux, dim3(1), dim3(kGridFinalThreads), 0, s, a, U, wk.rep.p, slot);
         PTV_HIP(hipGetLastError());
         return PTV_OK;
     }
-    int event(size_t k) {
-        if (wk.ev.size() <= k) wk.ev.resize(k + 1);
-        return wk.ev[k].record(s);
-    }
+    int event(size_t k) { return record_event(wk.ev, k, s); }
 
-    // events 2 .. 2 + batches bracket the polling batches; returns the median ms per iteration
+    // one solve; also returns the median ms per iteration over its polling batches
     int solve(double *h_final, double &ms_solve, double &ms_iter_median) {
         const size_t nbytes = (size_t)a.n * sizeof(double);
         PTV_TRY(event(2));
-        if (vec2) hipLaunchKernelGGL(k_rhs<2>, dim3(nb), dim3(kThreads), 0, s, a, wk.state.p, wk.div.p, M, wk.u.p, wk.part.p);
-        else hipLaunchKernelGGL(k_rhs<1>, dim3(nb), dim3(kThreads), 0, s, a, wk.state.p, wk.div.p, M, wk.u.p, wk.part.p);
-        PTV_HIP(hipGetLastError());
+        GRID_LAUNCH(k_rhs, vec2, nb, s, a, wk.state.p, wk.div.p, M, wk.u.p, wk.part.p);
         PTV_TRY(scalar(PH_INIT_BETA));
         PTV_HIP(hipMemsetAsync(wk.v.p, 0, nbytes, s));
         PTV_HIP(hipMemsetAsync(wk.w.p, 0, nbytes, s));
@@ -564,30 +527,17 @@ struct Solver {
         PTV_TRY(update());  // w = v
         PTV_TRY(event(3));
         const size_t sbytes = kStateLen * sizeof(double);
-        int batches = 0;
-        bool stopped = false;
         std::vector<int> batch_iters;
-        for (int done = 0; done < cfg.iter_lim && !stopped; done += kPoll, ++batches) {
-            const int cnt = std::min(kPoll, cfg.iter_lim - done);
-            for (int k = 0; k < cnt; ++k) {
-                PTV_TRY(bidiag(0));
-                PTV_TRY(scalar(PH_BETA));
-                PTV_TRY(bidiag(1));
-                PTV_TRY(scalar(PH_ALFA));
-                PTV_TRY(update());
-                PTV_TRY(scalar(PH_TEST));
-            }
-            batch_iters.push_back(cnt);
-            PTV_HIP(hipMemcpyAsync(wk.h_state.p + (batches & 1) * kStateLen, wk.state.p, sbytes, hipMemcpyDeviceToHost, s));
-            PTV_TRY(event(4 + batches));
-            if (batches >= 1) {  // poll one batch behind the enqueue: the device never waits for the host
-                PTV_HIP(hipEventSynchronize(wk.ev[4 + batches - 1]));
-                stopped = wk.h_state.p[((batches - 1) & 1) * kStateLen + S_STOP] != 0.0;
-            }
-        }
-        if (vec2) hipLaunchKernelGGL(k_nan<2>, dim3(nb), dim3(kThreads), 0, s, a, wk.x.p, wk.part.p);
-        else hipLaunchKernelGGL(k_nan<1>, dim3(nb), dim3(kThreads), 0, s, a, wk.x.p, wk.part.p);
-        PTV_HIP(hipGetLastError());
+        PTV_TRY(poll_batches(s, wk.state.p, wk.h_state.p, kStateLen, wk.ev, cfg.iter_lim, [&](int) -> int {
+            PTV_TRY(bidiag(0));
+            PTV_TRY(scalar(PH_BETA));
+            PTV_TRY(bidiag(1));
+            PTV_TRY(scalar(PH_ALFA));
+            PTV_TRY(update());
+            return scalar(PH_TEST);
+        }, batch_iters));
+        const size_t batches = batch_iters.size();
+        GRID_LAUNCH(k_nan, vec2, nb, s, a, wk.x.p, wk.part.p);
         PTV_TRY(scalar(PH_NAN));
         PTV_HIP(hipMemcpyAsync(h_final, wk.state.p, sbytes, hipMemcpyDeviceToHost, s));
         PTV_TRY(event(4 + batches));
@@ -607,9 +557,7 @@ int launch_clean_laplacian(const CleanGrid &g, const uint8_t *M, const double *x
     PTV_TRY(make_args(g, a));
     const bool vec2 = a.nx % 2 == 0 && all_aligned16(x, y) && aligned(M, 2);
     const unsigned nb = blocks_for(a.n, vec2 ? 2 : 1);
-    if (vec2) hipLaunchKernelGGL(k_laplacian<2>, dim3(nb), dim3(kThreads), 0, s, a, x, M, y);
-    else hipLaunchKernelGGL(k_laplacian<1>, dim3(nb), dim3(kThreads), 0, s, a, x, M, y);
-    PTV_HIP(hipGetLastError());
+    GRID_LAUNCH(k_laplacian, vec2, nb, s, a, x, M, y);
     return PTV_OK;
 }
 
@@ -619,9 +567,7 @@ int launch_clean_correction(const CleanGrid &g, const uint8_t *M, const double *
     PTV_TRY(make_args(g, a));
     const bool vec2 = a.nx % 2 == 0 && all_aligned16(U, V, W, phi, Uo, Vo, Wo) && aligned(M, 2);
     const unsigned nb = blocks_for(a.n, vec2 ? 2 : 1);
-    if (vec2) hipLaunchKernelGGL(k_correction<2>, dim3(nb), dim3(kThreads), 0, s, a, phi, M, U, V, W, Uo, Vo, Wo);
-    else hipLaunchKernelGGL(k_correction<1>, dim3(nb), dim3(kThreads), 0, s, a, phi, M, U, V, W, Uo, Vo, Wo);
-    PTV_HIP(hipGetLastError());
+    GRID_LAUNCH(k_correction, vec2, nb, s, a, phi, M, U, V, W, Uo, Vo, Wo);
     return PTV_OK;
 }
 
@@ -682,16 +628,7 @@ int clean_run(CleanWork &wk, const CleanGrid &g, const CleanSolve &sv, const uin
     double *h_final = wk.h_state.p + 2 * kStateLen, *h_rep = wk.h_state.p + 3 * kStateLen;
 
     Solver sol{wk, a, LsqrCfg{sv.damp, sv.atol, sv.btol, 1.0 / 1e8, sv.iter_lim}, M, s, vec2, nb};
-    DivArgs d{};
-    d.nx = a.nx;
-    d.ny = a.ny;
-    d.nz = a.nz;
-    d.z_begin = 0;
-    d.z_end = a.nz;
-    d.edge_lo = d.edge_hi = 1;
-    d.dx = g.dx;
-    d.dy = g.dy;
-    d.dz = g.dz;
+    const DivArgs d = full_grid_div(a, g.dx, g.dy, g.dz);
 
     ptv_clean_stats out{};
     PTV_TRY(sol.event(0));

@@ -1,4 +1,5 @@
-// ptv_grid_vec.hpp — what the dense-grid solvers share (ptv_clean.hip, ptv_variational.hip):
+// ptv_grid_vec.hpp — what the dense-grid solvers share (ptv_clean.hip, ptv_variational.hip,
+// ptv_pressure.hip; the scalar recurrence and the host loop above it are in ptv_grid_solve.hpp):
 // the one- or two-wide element groups of a lane, a group's position on the grid, the fixed-order
 // block sum and the layout of the per-block partial sums.
 //

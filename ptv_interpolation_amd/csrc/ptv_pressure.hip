@@ -35,48 +35,32 @@
 // k_pq recomputes the six neighbours' p' from r and p with the owners' expression.  Bytes per voxel
 // and iteration: k_pq 8 r + 8 p + 8 p' + 8 q + 1 mask = 33; k_pxr 8 p' + 8 q + 8 x + 8 r reads, 8 x +
 // 8 r writes + 1 = 49; 82 in all, + 2 with a Dirichlet grid (one byte in each pass).
-// Stopping, polling and the NaN outcome are ptv_variational.hip's.
+// The scalar recurrence with its stopping rules and NaN outcome, the stop flag and the polling loop
+// are those of ptv_grid_solve.hpp.
 #include <cmath>
 #include <algorithm>
 
 #include "ptv_pressure.hpp"
-#include "ptv_grid_vec.hpp"
-#include "ptv_kernels.hpp"
+#include "ptv_grid_solve.hpp"
 
 namespace ptv {
 
 namespace {
 
-constexpr int kPoll = 8;  // CG iterations between two polls of the stop flag
+using namespace cg;
 
-// device-resident state (doubles): the CG recurrence, then what the force pass leaves
-enum {
-    S_STOP = 0, S_INFO, S_ITN, S_RHO, S_RHO_PREV, S_BETA, S_ALPHA, S_RR, S_BNORM, S_THR, S_NAN, S_NDIR, S_NFLUID,
-    S_CG_COUNT,
-    F_BULK = 16, F_SFX, F_SFY, F_SFZ, F_SW, F_NFLUID, F_COUNT
-};
+// device-resident state (doubles): the CG recurrence, the solve's counts, then what the force pass leaves
+enum { S_NDIR = S_CG_COUNT, S_NFLUID, S_COUNT, F_BULK = 16, F_SFX, F_SFY, F_SFZ, F_SW, F_NFLUID, F_COUNT };
 constexpr int kStateLen = 24;
-static_assert(S_CG_COUNT <= F_BULK && F_COUNT <= kStateLen, "state length");
+static_assert(S_COUNT <= F_BULK && F_COUNT <= kStateLen, "state length");
 
-enum Phase { PH_BULK = 0, PH_FORCE, PH_INIT, PH_TOP0, PH_TOP, PH_ALPHA, PH_END };
+enum { PH_BULK = PH_CG_COUNT, PH_FORCE };
 enum Code : uint8_t { C_SOLID = 0, C_BULK = 1, C_FILL1 = 2, C_FILL2 = 3, C_OPEN = 4 };
 
 struct PArgs : GridDims {
     double h[3];    // dx, dy, dz
     double h2[3];   // h ** 2 (the raw Laplacian divides by it)
     double ih2[3];  // 1.0 / h ** 2 (the matrix entries, physics.py:68)
-};
-
-struct CgCfg {
-    double rtol;
-    int maxiter;
-};
-
-struct V3 {
-    double *c[3];
-};
-struct CV3 {
-    const double *c[3];
 };
 
 // the six neighbours of voxel (x, y, z) at index i, clamped at the array ends
@@ -468,92 +452,39 @@ __global__ __launch_bounds__(kGridThreads) void k_pout(PArgs a, const double *__
 }
 
 // Second reduction stage and the scalar steps.  One block sums the partials in a fixed order, then
-// thread 0 alone advances the state as scipy's cg does between its vector operations.
+// thread 0 alone advances the state: cg_step (PH_INIT also stores the Dirichlet and fluid counts),
+// or the force pass's sums.
 __global__ __launch_bounds__(kGridFinalThreads) void k_pcg_scalar(int phase, CgCfg cfg, double *__restrict__ st,
                                                                    const double *__restrict__ part, unsigned npart) {
-    const bool solver = phase == PH_TOP0 || phase == PH_TOP || phase == PH_ALPHA || phase == PH_END;
-    if (solver && st[S_STOP] != 0.0) return;
+    if (in_iteration(phase) && st[S_STOP] != 0.0) return;
     double r[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
     const int rows = phase == PH_FORCE ? 5 : phase == PH_INIT ? 3 : phase == PH_TOP0 ? 0 : 1;
     for (int k = 0; k < rows; ++k) r[k] = partial_sum(part + k * npart, npart);
     if (threadIdx.x != 0) return;
-    const double r0 = r[0];
-    switch (phase) {
-    case PH_BULK:
-        st[F_BULK] = r0;
-        break;
-    case PH_FORCE:
+    if (phase == PH_BULK) {
+        st[F_BULK] = r[0];
+    } else if (phase == PH_FORCE) {
         st[F_SFX] = r[0];
         st[F_SFY] = r[1];
         st[F_SFZ] = r[2];
         st[F_SW] = r[3];
         st[F_NFLUID] = r[4];
-        break;
-    case PH_INIT: {  // bnrm2, the threshold max(atol, rtol * bnrm2) with atol = 0, the early returns
-        const double bnorm = sqrt(r0);
-        for (int k = 0; k < S_CG_COUNT; ++k) st[k] = 0.0;
-        st[S_NDIR] = r[1];
-        st[S_NFLUID] = r[2];
-        st[S_RR] = r0;
-        st[S_BNORM] = bnorm;
-        st[S_THR] = cfg.rtol * bnorm > 0.0 ? cfg.rtol * bnorm : 0.0;
-        if (bnorm == 0.0 || cfg.maxiter <= 0) {
-            st[S_STOP] = 1.0;  // zeros, info = 0
-        } else if (r0 != r0) {  // a NaN in b: alpha is NaN in the first step and x is NaN from then on
-            st[S_NAN] = 1.0;
-            st[S_INFO] = (double)cfg.maxiter;
-            st[S_ITN] = (double)cfg.maxiter;
-            st[S_STOP] = 1.0;
+    } else {
+        cg_step(phase, cfg, st, r[0]);
+        if (phase == PH_INIT) {
+            st[S_NDIR] = r[1];
+            st[S_NFLUID] = r[2];
         }
-        break;
-    }
-    case PH_TOP0:
-    case PH_TOP: {  // the top of an iteration: the only convergence test, then rho and beta
-        const double rr = phase == PH_TOP0 ? st[S_RR] : r0;
-        st[S_RR] = rr;
-        if (sqrt(rr) < st[S_THR]) {
-            st[S_STOP] = 1.0;  // info = 0
-            break;
-        }
-        st[S_RHO] = rr;
-        st[S_BETA] = phase == PH_TOP0 ? 0.0 : rr / st[S_RHO_PREV];
-        break;
-    }
-    case PH_ALPHA:
-        st[S_ALPHA] = st[S_RHO] / r0;
-        st[S_RHO_PREV] = st[S_RHO];
-        st[S_ITN] += 1.0;  // this iteration's updates follow unconditionally
-        break;
-    case PH_END:  // the loop ran out: no test after the last step
-        st[S_RR] = r0;
-        st[S_INFO] = (double)cfg.maxiter;
-        st[S_STOP] = 1.0;
-        break;
-    default:
-        break;
     }
 }
 
 int make_args(const PressGrid &g, PArgs &a) {
-    if (g.nx <= 0 || g.ny <= 0 || g.nz <= 0) {
-        set_error("pressure: dimensions must be positive");
-        return PTV_E_ARG;
-    }
-    const long long n = (long long)g.nx * g.ny * g.nz;
-    if (n > 0x7fff0000LL) {
-        set_error("pressure: grids of 2^31 voxels or more are not supported");
-        return PTV_E_ARG;
-    }
+    PTV_TRY(grid_dims("pressure", g.nx, g.ny, g.nz, a));
     if (!(g.dx > 0.0) || !(g.dy > 0.0) || !(g.dz > 0.0) || !std::isfinite(g.dx) || !std::isfinite(g.dy) ||
         !std::isfinite(g.dz)) {
         set_error("pressure: spacings must be positive finite numbers");
         return PTV_E_ARG;
     }
-    a.nx = g.nx;
-    a.ny = g.ny;
-    a.nz = g.nz;
-    a.n = (unsigned)n;
-    a.plane = (unsigned)g.nx * (unsigned)g.ny;
     const double h[3] = {g.dx, g.dy, g.dz};
     for (int k = 0; k < 3; ++k) {
         a.h[k] = h[k];
@@ -563,22 +494,10 @@ int make_args(const PressGrid &g, PArgs &a) {
     return PTV_OK;
 }
 
-#define PRESS_LAUNCH(kernel, vec2, nb, s, ...)                                                            \
-    do {                                                                                                  \
-        if (vec2) hipLaunchKernelGGL(kernel<2>, dim3(nb), dim3(kGridThreads), 0, s, __VA_ARGS__);          \
-        else hipLaunchKernelGGL(kernel<1>, dim3(nb), dim3(kGridThreads), 0, s, __VA_ARGS__);               \
-        PTV_HIP(hipGetLastError());                                                                       \
-    } while (0)
-
 int scalar(PressWork &wk, int phase, const CgCfg &cfg, unsigned nb, hipStream_t s) {
     hipLaunchKernelGGL(k_pcg_scalar, dim3(1), dim3(kGridFinalThreads), 0, s, phase, cfg, wk.state.p, wk.part.p, nb);
     PTV_HIP(hipGetLastError());
     return PTV_OK;
-}
-
-int event(PressWork &wk, size_t k, hipStream_t s) {
-    if (wk.ev.size() <= k) wk.ev.resize(k + 1);
-    return wk.ev[k].record(s);
 }
 
 }  // namespace
@@ -606,9 +525,9 @@ int press_force(PressWork &wk, const PressGrid &g, double mu, double rho, const 
     PTV_TRY(wk.h_state.ensure(3 * kStateLen));
     double *h_final = wk.h_state.p + 2 * kStateLen;
     const CgCfg cfg{0.0, 0};
-    const V3 L{{wk.lap.p, wk.lap.p + n, wk.lap.p + 2 * n}};
-    const CV3 cL{{L.c[0], L.c[1], L.c[2]}}, F{{U, V, W}};
-    PTV_TRY(event(wk, 0, s));
+    const V3 L = parts(wk.lap.p, n);
+    const CV3 cL = cparts(wk.lap.p, n), F{{U, V, W}};
+    PTV_TRY(record_event(wk.ev, 0, s));
     hipLaunchKernelGGL(k_lap<1>, dim3(nb), dim3(kGridThreads), 0, s, a, F, M, L, wk.code.p, wk.part.p);
     PTV_HIP(hipGetLastError());
     PTV_TRY(scalar(wk, PH_BULK, cfg, nb, s));
@@ -619,7 +538,7 @@ int press_force(PressWork &wk, const PressGrid &g, double mu, double rho, const 
     PTV_HIP(hipGetLastError());
     PTV_TRY(scalar(wk, PH_FORCE, cfg, nb, s));
     PTV_HIP(hipMemcpyAsync(h_final, wk.state.p, kStateLen * sizeof(double), hipMemcpyDeviceToHost, s));
-    PTV_TRY(event(wk, 1, s));
+    PTV_TRY(record_event(wk.ev, 1, s));
     PTV_HIP(hipStreamSynchronize(s));
     if (st) {
         st->n_fluid = (int64_t)h_final[F_NFLUID];
@@ -640,7 +559,7 @@ int press_divergence(const PressGrid &g, bool inhomogeneous, const uint8_t *M, c
     PTV_TRY(make_args(g, a));
     const bool vec2 = a.nx % 2 == 0 && all_aligned16(D);
     const unsigned nb = blocks_for(a.n, vec2 ? 2 : 1);
-    PRESS_LAUNCH(k_fdiv, vec2, nb, s, a, inhomogeneous ? 1 : 0, CV3{{Fx, Fy, Fz}}, M, D);
+    GRID_LAUNCH(k_fdiv, vec2, nb, s, a, inhomogeneous ? 1 : 0, CV3{{Fx, Fy, Fz}}, M, D);
     return PTV_OK;
 }
 
@@ -677,38 +596,29 @@ int press_cg(PressWork &wk, const PressGrid &g, double rtol, int maxiter, const 
     const CgCfg cfg{rtol, maxiter};
     const double *cst = wk.state.p;
 
-    PTV_TRY(event(wk, 2, s));
+    PTV_TRY(record_event(wk.ev, 2, s));
     PTV_HIP(hipMemsetAsync(wk.p[0].p, 0, nbytes, s));
     PTV_HIP(hipMemsetAsync(wk.p[1].p, 0, nbytes, s));
     PTV_HIP(hipMemsetAsync(wk.q.p, 0, nbytes, s));
-    PRESS_LAUNCH(k_pinit, vec2, nb, s, a, B, M, Dir, wk.x.p, wk.r.p, wk.part.p, nb);
+    GRID_LAUNCH(k_pinit, vec2, nb, s, a, B, M, Dir, wk.x.p, wk.r.p, wk.part.p, nb);
     PTV_TRY(scalar(wk, PH_INIT, cfg, nb, s));
-    PTV_TRY(event(wk, 3, s));
-    int batches = 0, cur = 0;  // p[cur] holds the last direction
-    bool stopped = false;
+    PTV_TRY(record_event(wk.ev, 3, s));
+    int cur = 0;  // p[cur] holds the last direction
     std::vector<int> batch_iters;
-    for (int done = 0; done < maxiter && !stopped; done += kPoll, ++batches) {
-        const int cnt = std::min(kPoll, maxiter - done);
-        for (int k = 0; k < cnt; ++k) {
-            PTV_TRY(scalar(wk, done + k == 0 ? PH_TOP0 : PH_TOP, cfg, nb, s));
-            PRESS_LAUNCH(k_pq, vec2, nb, s, a, cst, (const double *)wk.r.p, (const double *)wk.p[cur].p,
-                         wk.p[cur ^ 1].p, wk.q.p, M, Dir, wk.part.p);
-            cur ^= 1;
-            PTV_TRY(scalar(wk, PH_ALPHA, cfg, nb, s));
-            PRESS_LAUNCH(k_pxr, vec2, nb, s, a, cst, (const double *)wk.p[cur].p, (const double *)wk.q.p, wk.x.p,
-                         wk.r.p, M, Dir, wk.part.p);
-        }
-        batch_iters.push_back(cnt);
-        PTV_HIP(hipMemcpyAsync(wk.h_state.p + (batches & 1) * kStateLen, wk.state.p, sbytes, hipMemcpyDeviceToHost, s));
-        PTV_TRY(event(wk, 4 + batches, s));
-        if (batches >= 1) {  // poll one batch behind the enqueue: the device never waits for the host
-            PTV_HIP(hipEventSynchronize(wk.ev[4 + batches - 1]));
-            stopped = wk.h_state.p[((batches - 1) & 1) * kStateLen + S_STOP] != 0.0;
-        }
-    }
+    PTV_TRY(poll_batches(s, wk.state.p, wk.h_state.p, kStateLen, wk.ev, maxiter, [&](int it) -> int {
+        PTV_TRY(scalar(wk, it == 0 ? PH_TOP0 : PH_TOP, cfg, nb, s));
+        GRID_LAUNCH(k_pq, vec2, nb, s, a, cst, (const double *)wk.r.p, (const double *)wk.p[cur].p, wk.p[cur ^ 1].p,
+                    wk.q.p, M, Dir, wk.part.p);
+        cur ^= 1;
+        PTV_TRY(scalar(wk, PH_ALPHA, cfg, nb, s));
+        GRID_LAUNCH(k_pxr, vec2, nb, s, a, cst, (const double *)wk.p[cur].p, (const double *)wk.q.p, wk.x.p, wk.r.p, M,
+                    Dir, wk.part.p);
+        return PTV_OK;
+    }, batch_iters));
+    const size_t batches = batch_iters.size();
     PTV_TRY(scalar(wk, PH_END, cfg, nb, s));
-    PTV_TRY(event(wk, 4 + batches, s));
-    PRESS_LAUNCH(k_pout, vec2, nb, s, a, cst, (const double *)wk.x.p, M, Dir, X);
+    PTV_TRY(record_event(wk.ev, 4 + batches, s));
+    GRID_LAUNCH(k_pout, vec2, nb, s, a, cst, (const double *)wk.x.p, M, Dir, X);
     PTV_HIP(hipMemcpyAsync(h_final, wk.state.p, sbytes, hipMemcpyDeviceToHost, s));
     PTV_HIP(hipStreamSynchronize(s));
     if (st) {

@@ -33,48 +33,30 @@
 // (stencil neighbours come from the cache lines of adjacent lanes and rows).
 //
 // Reductions are the two-stage fixed-order sums of ptv_grid_vec.hpp: no floating-point atomics, a
-// call repeats bit for bit.  Every kernel returns at once when the state's stop flag is set; the
-// host polls a pinned copy of the state once per kPoll iterations, one batch behind the enqueue.
-// scipy tests only at the top of an iteration: after the last one nothing is tested, and info =
-// maxiter is returned even when r is 0.
+// call repeats bit for bit.  The scalar recurrence with its stopping rules, the stop flag and the
+// polling loop are those of ptv_grid_solve.hpp.
 #include <cmath>
 #include <algorithm>
 
 #include "ptv_variational.hpp"
-#include "ptv_grid_vec.hpp"
-#include "ptv_kernels.hpp"
+#include "ptv_grid_solve.hpp"
 
 namespace ptv {
 
 namespace {
 
-constexpr int kPoll = 8;  // CG iterations between two polls of the stop flag
+using namespace cg;
 
-// device-resident CG state (doubles)
-enum {
-    S_STOP = 0, S_INFO, S_ITN, S_RHO, S_RHO_PREV, S_BETA, S_ALPHA, S_RR, S_BNORM, S_THR, S_NAN, S_NFLUID,
-    S_DIV0, S_DIV1, S_COUNT
-};
+// device-resident state (doubles): the CG recurrence, then the report's slots
+enum { S_NFLUID = S_CG_COUNT, S_DIV0, S_DIV1, S_COUNT };
 constexpr int kStateLen = 16;
 static_assert(S_COUNT <= kStateLen, "state length");
 
-enum Phase { PH_DIV = 0, PH_INIT, PH_TOP0, PH_TOP, PH_ALPHA, PH_END };
+enum { PH_DIV = PH_CG_COUNT };
 
 struct VarArgs : GridDims {
     double ch[3], eh[3];  // 0.5 / h and 1.0 / h for x, y, z (physics.py:406-414)
     double lambda;
-};
-
-struct CgCfg {
-    double rtol;
-    int maxiter;
-};
-
-struct V3 {
-    double *c[3];
-};
-struct CV3 {
-    const double *c[3];
 };
 
 // The stencil of a group: which neighbours are fluid voxels inside the grid, the diagonal
@@ -377,13 +359,12 @@ __global__ __launch_bounds__(kGridThreads) void k_out(VarArgs a, const double *_
     }
 }
 
-// Second reduction stage and the scalar recurrence.  One block sums the partials in a fixed order,
-// then thread 0 alone advances the state as scipy's cg does between its vector operations.
+// Second reduction stage and the scalar step.  One block sums the partials in a fixed order, then
+// thread 0 alone advances the state: cg_step, or the report's mean |div| into slot S_DIV0 + slot.
 __global__ __launch_bounds__(kGridFinalThreads) void k_cg_scalar(int phase, CgCfg cfg, double *__restrict__ st,
                                                                   const double *__restrict__ part, unsigned npart,
                                                                   int slot) {
-    const bool solver = phase == PH_TOP0 || phase == PH_TOP || phase == PH_ALPHA || phase == PH_END;
-    if (solver && st[S_STOP] != 0.0) return;
+    if (in_iteration(phase) && st[S_STOP] != 0.0) return;
     double r0 = 0.0, r1 = 0.0;
     if (phase == PH_DIV) {
         r0 = partial_sum(part + npart, npart);      // sum |div|
@@ -392,64 +373,16 @@ __global__ __launch_bounds__(kGridFinalThreads) void k_cg_scalar(int phase, CgCf
         r0 = partial_sum(part, npart);
     }
     if (threadIdx.x != 0) return;
-    switch (phase) {
-    case PH_DIV:
+    if (phase == PH_DIV) {
         st[S_NFLUID] = r1;
         st[S_DIV0 + slot] = r0 / r1;
-        break;
-    case PH_INIT: {  // bnrm2, the threshold max(atol, rtol * bnrm2) with atol = 0, the early returns
-        const double bnorm = sqrt(r0);
-        for (int k = 0; k < S_NFLUID; ++k) st[k] = 0.0;
-        st[S_RR] = r0;
-        st[S_BNORM] = bnorm;
-        st[S_THR] = cfg.rtol * bnorm > 0.0 ? cfg.rtol * bnorm : 0.0;
-        if (bnorm == 0.0 || cfg.maxiter <= 0) {
-            st[S_STOP] = 1.0;  // zeros, info = 0
-        } else if (r0 != r0) {  // a NaN in b: alpha is NaN in the first step and x is NaN from then on
-            st[S_NAN] = 1.0;
-            st[S_INFO] = (double)cfg.maxiter;
-            st[S_ITN] = (double)cfg.maxiter;
-            st[S_STOP] = 1.0;
-        }
-        break;
-    }
-    case PH_TOP0:
-    case PH_TOP: {  // the top of an iteration: the only convergence test, then rho and beta
-        const double rr = phase == PH_TOP0 ? st[S_RR] : r0;
-        st[S_RR] = rr;
-        if (sqrt(rr) < st[S_THR]) {
-            st[S_STOP] = 1.0;  // info = 0
-            break;
-        }
-        st[S_RHO] = rr;
-        st[S_BETA] = phase == PH_TOP0 ? 0.0 : rr / st[S_RHO_PREV];
-        break;
-    }
-    case PH_ALPHA:
-        st[S_ALPHA] = st[S_RHO] / r0;
-        st[S_RHO_PREV] = st[S_RHO];
-        st[S_ITN] += 1.0;  // this iteration's updates follow unconditionally
-        break;
-    case PH_END:  // the loop ran out: no test after the last step
-        st[S_RR] = r0;
-        st[S_INFO] = (double)cfg.maxiter;
-        st[S_STOP] = 1.0;
-        break;
-    default:
-        break;
+    } else {
+        cg_step(phase, cfg, st, r0);
     }
 }
 
 int make_args(const VarGrid &g, double lambda_reg, VarArgs &a) {
-    if (g.nx <= 0 || g.ny <= 0 || g.nz <= 0) {
-        set_error("variational: dimensions must be positive");
-        return PTV_E_ARG;
-    }
-    const long long n = (long long)g.nx * g.ny * g.nz;
-    if (n > 0x7fff0000LL) {
-        set_error("variational: grids of 2^31 voxels or more are not supported");
-        return PTV_E_ARG;
-    }
+    PTV_TRY(grid_dims("variational", g.nx, g.ny, g.nz, a));
     if (!(g.dx > 0.0) || !(g.dy > 0.0) || !(g.dz > 0.0) || !std::isfinite(g.dx) || !std::isfinite(g.dy) ||
         !std::isfinite(g.dz)) {
         set_error("variational: spacings must be positive finite numbers");
@@ -463,11 +396,6 @@ int make_args(const VarGrid &g, double lambda_reg, VarArgs &a) {
         set_error("variational: lambda_reg < 0 (the system is not positive definite)");
         return PTV_E_UNSUPPORTED;
     }
-    a.nx = g.nx;
-    a.ny = g.ny;
-    a.nz = g.nz;
-    a.n = (unsigned)n;
-    a.plane = (unsigned)g.nx * (unsigned)g.ny;
     const double h[3] = {g.dx, g.dy, g.dz};
     for (int k = 0; k < 3; ++k) {
         a.ch[k] = 0.5 / h[k];
@@ -477,16 +405,6 @@ int make_args(const VarGrid &g, double lambda_reg, VarArgs &a) {
     return PTV_OK;
 }
 
-#define VAR_LAUNCH(kernel, vec2, nb, s, ...)                                                              \
-    do {                                                                                                  \
-        if (vec2) hipLaunchKernelGGL(kernel<2>, dim3(nb), dim3(kGridThreads), 0, s, __VA_ARGS__);          \
-        else hipLaunchKernelGGL(kernel<1>, dim3(nb), dim3(kGridThreads), 0, s, __VA_ARGS__);               \
-        PTV_HIP(hipGetLastError());                                                                       \
-    } while (0)
-
-V3 parts(double *base, size_t n) { return V3{{base, base + n, base + 2 * n}}; }
-CV3 cparts(const double *base, size_t n) { return CV3{{base, base + n, base + 2 * n}}; }
-
 }  // namespace
 
 int launch_var_divergence(const VarGrid &g, const uint8_t *M, const double *xu, const double *xv, const double *xw,
@@ -495,7 +413,7 @@ int launch_var_divergence(const VarGrid &g, const uint8_t *M, const double *xu, 
     PTV_TRY(make_args(g, 0.0, a));
     const bool vec2 = a.nx % 2 == 0 && all_aligned16(xu, xv, xw, d) && aligned(M, 2);
     const unsigned nb = blocks_for(a.n, vec2 ? 2 : 1);
-    VAR_LAUNCH(k_var_div, vec2, nb, s, a, CV3{{xu, xv, xw}}, M, d);
+    GRID_LAUNCH(k_var_div, vec2, nb, s, a, CV3{{xu, xv, xw}}, M, d);
     return PTV_OK;
 }
 
@@ -507,7 +425,7 @@ int launch_var_adjoint(const VarGrid &g, double lambda_reg, const uint8_t *M, co
     const bool vec2 = a.nx % 2 == 0 && all_aligned16(d, xu, xv, xw, yu, yv, yw) && aligned(M, 2);
     const unsigned nb = blocks_for(a.n, vec2 ? 2 : 1);
     PTV_TRY(part.ensure(nb));
-    VAR_LAUNCH(k_q, vec2, nb, s, a, (const double *)nullptr, d, CV3{{xu, xv, xw}}, V3{{yu, yv, yw}}, M, part.p);
+    GRID_LAUNCH(k_q, vec2, nb, s, a, (const double *)nullptr, d, CV3{{xu, xv, xw}}, V3{{yu, yv, yw}}, M, part.p);
     return PTV_OK;
 }
 
@@ -533,30 +451,18 @@ int variational_run(VarWork &wk, const VarGrid &g, const VarSolve &sv, const uin
     double *h_final = wk.h_state.p + 2 * kStateLen;
     const size_t sbytes = kStateLen * sizeof(double);
     const CgCfg cfg{sv.rtol, sv.maxiter};
-    auto event = [&](size_t k) {
-        if (wk.ev.size() <= k) wk.ev.resize(k + 1);
-        return wk.ev[k].record(s);
-    };
+    auto event = [&](size_t k) { return record_event(wk.ev, k, s); };
     auto scalar = [&](int phase, int slot) {
         hipLaunchKernelGGL(k_cg_scalar, dim3(1), dim3(kGridFinalThreads), 0, s, phase, cfg, wk.state.p, wk.part.p, nb,
                            slot);
         PTV_HIP(hipGetLastError());
         return PTV_OK;
     };
-    DivArgs d{};
-    d.nx = a.nx;
-    d.ny = a.ny;
-    d.nz = a.nz;
-    d.z_begin = 0;
-    d.z_end = a.nz;
-    d.edge_lo = d.edge_hi = 1;
-    d.dx = g.dx;
-    d.dy = g.dy;
-    d.dz = g.dz;
+    const DivArgs d = full_grid_div(a, g.dx, g.dy, g.dz);
     // mean |div| over the fluid voxels of three fields into state slot S_DIV0 + slot (physics.py:503-504)
     auto mean_abs_div = [&](const double *fu, const double *fv, const double *fw, int slot) {
         PTV_TRY(launch_divergence(d, fu, fv, fw, M, wk.div.p, s));
-        VAR_LAUNCH(k_div_stats, vec2, nb, s, (GridDims)a, wk.div.p, M, wk.part.p, nb);
+        GRID_LAUNCH(k_div_stats, vec2, nb, s, (GridDims)a, wk.div.p, M, wk.part.p, nb);
         return scalar(PH_DIV, slot);
     };
 
@@ -577,35 +483,26 @@ int variational_run(VarWork &wk, const VarGrid &g, const VarSolve &sv, const uin
     PTV_TRY(event(2));
     for (DevBuf<double> *b : {&wk.p[0], &wk.p[1], &wk.q}) PTV_HIP(hipMemsetAsync(b->p, 0, 3 * n * sizeof(double), s));
     PTV_HIP(hipMemsetAsync(wk.d.p, 0, n * sizeof(double), s));
-    VAR_LAUNCH(k_init, vec2, nb, s, a, CV3{{U, V, W}}, M, X, R, wk.part.p);
+    GRID_LAUNCH(k_init, vec2, nb, s, a, CV3{{U, V, W}}, M, X, R, wk.part.p);
     PTV_TRY(scalar(PH_INIT, 0));
     PTV_TRY(event(3));
-    int batches = 0, cur = 0;  // p[cur] holds the last direction
-    bool stopped = false;
+    int cur = 0;  // p[cur] holds the last direction
     std::vector<int> batch_iters;
-    for (int done = 0; done < sv.maxiter && !stopped; done += kPoll, ++batches) {
-        const int cnt = std::min(kPoll, sv.maxiter - done);
-        for (int k = 0; k < cnt; ++k) {
-            PTV_TRY(scalar(done + k == 0 ? PH_TOP0 : PH_TOP, 0));
-            VAR_LAUNCH(k_dir, vec2, nb, s, a, (const double *)wk.state.p, cR, cparts(wk.p[cur].p, n),
-                       parts(wk.p[cur ^ 1].p, n), M, wk.d.p);
-            cur ^= 1;
-            const CV3 cP = cparts(wk.p[cur].p, n);
-            VAR_LAUNCH(k_q, vec2, nb, s, a, (const double *)wk.state.p, (const double *)wk.d.p, cP, Q, M, wk.part.p);
-            PTV_TRY(scalar(PH_ALPHA, 0));
-            VAR_LAUNCH(k_xr, vec2, nb, s, a, (const double *)wk.state.p, cP, cQ, X, R, M, wk.part.p);
-        }
-        batch_iters.push_back(cnt);
-        PTV_HIP(hipMemcpyAsync(wk.h_state.p + (batches & 1) * kStateLen, wk.state.p, sbytes, hipMemcpyDeviceToHost, s));
-        PTV_TRY(event(4 + batches));
-        if (batches >= 1) {  // poll one batch behind the enqueue: the device never waits for the host
-            PTV_HIP(hipEventSynchronize(wk.ev[4 + batches - 1]));
-            stopped = wk.h_state.p[((batches - 1) & 1) * kStateLen + S_STOP] != 0.0;
-        }
-    }
+    PTV_TRY(poll_batches(s, wk.state.p, wk.h_state.p, kStateLen, wk.ev, sv.maxiter, [&](int it) -> int {
+        PTV_TRY(scalar(it == 0 ? PH_TOP0 : PH_TOP, 0));
+        GRID_LAUNCH(k_dir, vec2, nb, s, a, (const double *)wk.state.p, cR, cparts(wk.p[cur].p, n),
+                    parts(wk.p[cur ^ 1].p, n), M, wk.d.p);
+        cur ^= 1;
+        const CV3 cP = cparts(wk.p[cur].p, n);
+        GRID_LAUNCH(k_q, vec2, nb, s, a, (const double *)wk.state.p, (const double *)wk.d.p, cP, Q, M, wk.part.p);
+        PTV_TRY(scalar(PH_ALPHA, 0));
+        GRID_LAUNCH(k_xr, vec2, nb, s, a, (const double *)wk.state.p, cP, cQ, X, R, M, wk.part.p);
+        return PTV_OK;
+    }, batch_iters));
+    const size_t batches = batch_iters.size();
     PTV_TRY(scalar(PH_END, 0));
     PTV_TRY(event(4 + batches));
-    VAR_LAUNCH(k_out, vec2, nb, s, a, (const double *)wk.state.p, cparts(wk.x.p, n), M, V3{{Uo, Vo, Wo}});
+    GRID_LAUNCH(k_out, vec2, nb, s, a, (const double *)wk.state.p, cparts(wk.x.p, n), M, V3{{Uo, Vo, Wo}});
     PTV_TRY(mean_abs_div(Uo, Vo, Wo, 1));
     PTV_HIP(hipMemcpyAsync(h_final, wk.state.p, sbytes, hipMemcpyDeviceToHost, s));
     PTV_TRY(event(1));
