@@ -445,6 +445,14 @@ def interp_grid_parallel(points, values, ax, ay, az, method="idw", k=8, power=2.
 #   c_i = ((0 + T_i0 (x_0 - r_0)) + T_i1 (x_1 - r_1)) + T_i2 (x_2 - r_2), c_3 = ((1 - c_0) - c_1) - c_2
 #   out = (((0 + c_0 v_s0) + c_1 v_s1) + c_2 v_s2) + c_3 v_s3,  fill_value where no simplex.
 # Pinned bit-exactly by tests/golden/linear_*.npz (the reference interpolate_field itself).
+# One constant differs: where a walk meets a degenerate simplex and the brute-force scan takes
+# over, find_simplex tests that simplex's neighbours with eps_broad = sqrt(100 DBL_EPSILON)
+# (1.49e-7), LinearNDInterpolator (and k_linear_brute) with sqrt(DBL_EPSILON) (1.49e-8), so the
+# two can locate a point differently only if a coordinate towards a flat simplex lies in
+# [-1.49e-7, -1.49e-8).  tests/test_linear_ref.py settles the interpolator's constant with probes
+# in that band and asserts that no voxel of the suite's lattice grids is in it
+# (test_find_simplex_route_cannot_differ_on_the_fixtures); without degenerate simplices the
+# constant is never read.  tests/_linear_ref.py restates the scan with either constant.
 # ---------------------------------------------------------------------------
 def linear_points(points, values, queries, fill_value=0.0, tri=None):
     from scipy.spatial import Delaunay

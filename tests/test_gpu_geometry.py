@@ -263,9 +263,11 @@ def test_linear_voxels_on_vertices_and_bounds(ctx):
     """A grid whose axes are the coordinates of 5 particles plus tri.min_bound / tri.max_bound: voxels
     exactly on vertices (where every incident simplex is a valid answer) and exactly on the bounding
     box test of the point location.  Normwise <= 1e-12 (any incident simplex interpolates the vertex
-    to rounding); the share of differing voxels is printed."""
+    to rounding); the share of differing voxels is printed.  Every voxel carries the bits of a simplex
+    that scipy's rule accepts (tests/_linear_ref.py)."""
     from ptv_interpolation_amd import _lib
     from scipy.spatial import Delaunay
+    from tests import _linear_ref as R
 
     P, Q, *_ = G.case("base")
     d = Delaunay(P)
@@ -282,6 +284,7 @@ def test_linear_voxels_on_vertices_and_bounds(ctx):
               f"normwise {normwise(a.ravel(), ref[:, c]):.2e}")
         assert normwise(a.ravel(), ref[:, c]) <= TOL_LINEAR
         assert normwise(a.ravel()[on_vertex], Q[pick, c]) <= TOL_LINEAR  # a vertex takes its own value
+    assert len(R.unexplained(got, R.admissible(d, Q, q, -7.5, R.EPS_BROAD))) == 0
 
 
 # ---------------------------------------------------------------------------------------------

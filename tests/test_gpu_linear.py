@@ -102,8 +102,10 @@ def test_mask_nan_to_num_and_fill_value(ctx):
 def test_lattice_degenerate_simplices_take_the_brute_force(ctx):
     """An exact 6^3 lattice: Qhull returns flat simplices (NaN transforms), so some walks fall
     back to scipy's brute-force scan (counted in stats['n_singular']).  Query points off the
-    lattice planes; agreement with the oracle to rounding (ties between neighbouring simplices)."""
+    lattice planes; agreement with the oracle to rounding (ties between neighbouring simplices), and
+    every voxel the bits of a simplex scipy's rule accepts (tests/_linear_ref.py)."""
     from oracle import cpu_ref
+    from tests import _linear_ref as R
     from ptv_interpolation_amd import _lib
     from scipy.spatial import Delaunay
 
@@ -116,9 +118,11 @@ def test_lattice_degenerate_simplices_take_the_brute_force(ctx):
     got = ctx.interp_linear(P, Q, tri, axes=(ax, ax, ax))
     ref = cpu_ref.linear_grid(P, Q, ax, ax, ax)
     print("brute-force voxels:", ctx.stats["n_singular"])
+    assert ctx.stats["n_singular"] > 0
     for a, b in zip(got, ref):
         assert normwise(a, b) <= 1e-12
         assert np.mean(a != b) < 0.05
+    assert len(R.unexplained(got, R.admissible(Delaunay(P), Q, R.grid_queries(ax, ax, ax), 0.0, R.EPS_BROAD))) == 0
 
 
 def test_sphere_pack_sampled(ctx):
