@@ -21,7 +21,8 @@ LIB = os.path.join(HERE, "libptv_amd.so")
 BUILD = os.path.join(HERE, "csrc", "_build")
 # the k-NN kernel's list lengths compile in parallel (ptv_knn_k*.hip instantiate ptv_knn_impl.hpp)
 KNN_PARTS = ["ptv_knn_k" + g + ".hip" for g in "abcdefgh"]
-SOURCES = (["ptv_api.cpp", "ptv_search.cpp", "ptv_run_knn.cpp", "ptv_run_chunked.cpp", "ptv_mesh_api.cpp", "ptv_mesh.hip",
+SOURCES = (["ptv_api.cpp", "ptv_search.cpp", "ptv_run_knn.cpp", "ptv_run_chunked.cpp",
+            "ptv_grid_api.cpp", "ptv_flow_api.cpp", "ptv_mask_api.cpp", "ptv_mesh_api.cpp", "ptv_mesh.hip",
             "ptv_surface_api.cpp", "ptv_surface.hip", "ptv_label_api.cpp", "ptv_label.hip",
             "ptv_bin.hip", "ptv_knn.hip"] + KNN_PARTS +
            ["ptv_rbf.hip"] + ["ptv_rbf_ns_" + g + ".hip" for g in "abcd"] +

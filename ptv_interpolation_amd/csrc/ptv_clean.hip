@@ -461,7 +461,7 @@ __global__ __launch_bounds__(kGridThreads) void k_correction(CleanArgs a, const 
     }
 }
 
-int make_args(const CleanGrid &g, CleanArgs &a) {
+int make_args(const GridSpec &g, CleanArgs &a) {
     PTV_TRY(grid_dims("clean", g.nx, g.ny, g.nz, a));
     if (!(g.dx != 0.0) || !(g.dy != 0.0) || !(g.dz != 0.0) || std::isnan(g.dx) || std::isnan(g.dy) ||
         std::isnan(g.dz)) {
@@ -552,7 +552,7 @@ struct Solver {
 
 }  // namespace
 
-int launch_clean_laplacian(const CleanGrid &g, const uint8_t *M, const double *x, double *y, hipStream_t s) {
+int launch_clean_laplacian(const GridSpec &g, const uint8_t *M, const double *x, double *y, hipStream_t s) {
     CleanArgs a{};
     PTV_TRY(make_args(g, a));
     const bool vec2 = a.nx % 2 == 0 && all_aligned16(x, y) && aligned(M, 2);
@@ -561,7 +561,7 @@ int launch_clean_laplacian(const CleanGrid &g, const uint8_t *M, const double *x
     return PTV_OK;
 }
 
-int launch_clean_correction(const CleanGrid &g, const uint8_t *M, const double *U, const double *V, const double *W,
+int launch_clean_correction(const GridSpec &g, const uint8_t *M, const double *U, const double *V, const double *W,
                             const double *phi, double *Uo, double *Vo, double *Wo, hipStream_t s) {
     CleanArgs a{};
     PTV_TRY(make_args(g, a));
@@ -571,7 +571,7 @@ int launch_clean_correction(const CleanGrid &g, const uint8_t *M, const double *
     return PTV_OK;
 }
 
-int clean_solve_rhs(CleanWork &wk, const CleanGrid &g, const CleanSolve &sv, const uint8_t *M, const double *rhs,
+int clean_solve_rhs(CleanWork &wk, const GridSpec &g, const CleanSolve &sv, const uint8_t *M, const double *rhs,
                     double *X, hipStream_t s, CleanRhsResult *res) {
     CleanArgs a{};
     PTV_TRY(make_args(g, a));
@@ -608,7 +608,7 @@ int clean_solve_rhs(CleanWork &wk, const CleanGrid &g, const CleanSolve &sv, con
     return PTV_OK;
 }
 
-int clean_run(CleanWork &wk, const CleanGrid &g, const CleanSolve &sv, const uint8_t *M, const double *U,
+int clean_run(CleanWork &wk, const GridSpec &g, const CleanSolve &sv, const uint8_t *M, const double *U,
               const double *V, const double *W, double *Uo, double *Vo, double *Wo, hipStream_t s,
               ptv_clean_stats *st) {
     CleanArgs a{};

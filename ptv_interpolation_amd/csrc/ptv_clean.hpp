@@ -11,11 +11,6 @@
 
 namespace ptv {
 
-struct CleanGrid {
-    int nx, ny, nz;
-    double dx, dy, dz;
-};
-
 // grow-only device scratch of the solver, owned by the context
 struct CleanWork {
     DevBuf<double> u, v, w, x, div;  // LSQR vectors (dense grids, solid entries 0) and the divergence
@@ -33,7 +28,7 @@ struct CleanSolve {
 };
 
 // all pointers device memory; Uo, Vo, Wo may alias U, V, W.  Synchronises `s`.
-int clean_run(CleanWork &wk, const CleanGrid &g, const CleanSolve &sv, const uint8_t *M, const double *U,
+int clean_run(CleanWork &wk, const GridSpec &g, const CleanSolve &sv, const uint8_t *M, const double *U,
               const double *V, const double *W, double *Uo, double *Vo, double *Wo, hipStream_t s,
               ptv_clean_stats *st);
 // One LSQR solve of A x = rhs - mean(rhs over fluid) for a caller's device right-hand side
@@ -44,10 +39,10 @@ struct CleanRhsResult {
     int istop, itn;
     double bnorm, rnorm, ms_solve, ms_iter_median;
 };
-int clean_solve_rhs(CleanWork &wk, const CleanGrid &g, const CleanSolve &sv, const uint8_t *M, const double *rhs,
+int clean_solve_rhs(CleanWork &wk, const GridSpec &g, const CleanSolve &sv, const uint8_t *M, const double *rhs,
                     double *X, hipStream_t s, CleanRhsResult *res);
-int launch_clean_correction(const CleanGrid &g, const uint8_t *M, const double *U, const double *V, const double *W,
+int launch_clean_correction(const GridSpec &g, const uint8_t *M, const double *U, const double *V, const double *W,
                             const double *phi, double *Uo, double *Vo, double *Wo, hipStream_t s);
-int launch_clean_laplacian(const CleanGrid &g, const uint8_t *M, const double *x, double *y, hipStream_t s);
+int launch_clean_laplacian(const GridSpec &g, const uint8_t *M, const double *x, double *y, hipStream_t s);
 
 }  // namespace ptv

@@ -57,6 +57,13 @@ struct CellGrid {
     long long ncells;
 };
 
+// The dense grid of a solver call (projection and variational cleaning, pressure recovery):
+// (nz, ny, nx) voxels in C order and their spacings.
+struct GridSpec {
+    int nx, ny, nz;
+    double dx, dy, dz;
+};
+
 // Device buffers produced by binning (owned by the context).
 struct Binned {
     const double4 *prec;     // sorted (x, y, z, original index as double)

@@ -23,6 +23,9 @@
 namespace ptv {
 
 constexpr int kMaxLattice = 6;
+// Slots of the context's staging pool: the largest host call, flow analysis, stages three fields
+// and four results.
+constexpr int kStageSlots = 7;
 
 // PTV_FLAG_SLAB_CULL_AUTO: the key of the cached cull map, and what the last proven culled call
 // under that key kept (the speculative reuse checks both on the device)
@@ -74,7 +77,9 @@ struct ptv_ctx {
     ptv::DevBuf<uint32_t> rbf_nslist;                                 // local RBF: voxels k_rbf_ns hands over
     ptv::DevBuf<int> rbf_cflag;                                       // local RBF: per chunk flagged / overflow
     ptv::DevBuf<double> smooth;                                       // per-particle smoothing (host calls)
-    ptv::DevBuf<uint8_t> fld[4];                                      // divergence host calls: U, V, W, out
+    // The one pool of the grid-field host calls (ptv_stage.hpp), slots sized in bytes.  A call
+    // stages its host arrays and results here and leaves nothing that a later call reads.
+    ptv::DevBuf<uint8_t> stage[ptv::kStageSlots];
     ptv::DevBuf<double> mask_axes;                                    // sample_mask: raw axes (ascending)
     ptv::DevBuf<int> mask_tabs;                                       // sample_mask: per-axis index tables
     ptv::DevBuf<uint8_t> mask_raw, mask_out;                          // sample_mask host calls
@@ -98,23 +103,15 @@ struct ptv_ctx {
     ptv::DevBuf<double> lin_tr;
     ptv::DevBuf<long long> lin_flags;                                 // linear: voxels left to the brute force
     ptv::CleanWork clean;                                             // divergence cleaning: LSQR vectors, state
-    ptv::DevBuf<double> clean_fld[4];                                 // its host calls: U, V, W (in place), phi / x
     ptv::VarWork var;                                                 // variational cleaning: CG vectors, state
-    ptv::DevBuf<double> var_fld[6];                                   // its host calls: fields (in place) / x, y
     ptv::PressWork press;                                             // pressure recovery: stencil scratch, CG vectors
-    ptv::DevBuf<double> press_fld[7];                                 // its host calls: U, V, W | F, rhs / x
-    ptv::DevBuf<uint8_t> press_dir;                                   //   and the Dirichlet grid
     ptv::Event ev_press[4];                                           // chain start, around the divergence, end
-    ptv::DevBuf<double> flow_part, flow_res;                        // flow analysis: per-block partials, reduced rows
-    ptv::DevBuf<uint8_t> flow_fld[3], flow_out[4];                   // its host calls: inputs (U, V, W | S, O), outputs
+    ptv::DevBuf<double> flow_part, flow_res;                          // flow analysis: per-block partials, reduced rows
     ptv::Event ev_flow0, ev_flow1;                                    // around its kernels
     ptv::DevBuf<double> drag_part, drag_res;                          // interface drag / gradient sums: partials, rows
-    ptv::DevBuf<int> drag_labels, drag_mask;                          // the label table; the mask of the host calls
-    ptv::DevBuf<uint8_t> drag_fld[4];                                 // the host calls' U, V, W, P
+    ptv::DevBuf<int> drag_labels;                                     // the label table
     ptv::Event ev_drag0, ev_drag1;                                    // around its kernels
     ptv::DevBuf<unsigned> edt_a, edt_b, edt_max;                      // distance transform: pass buffers, max(d2)
-    ptv::DevBuf<uint8_t> edt_mask;                                    // its host calls: the mask
-    ptv::DevBuf<int> edt_d2;                                          //   and d2
     ptv::DevBuf<double> align_dt, align_pts;                          // alignment score: resident field and points
     int64_t align_dt_dims[3] = {0, 0, 0};                             //   what they hold (nx, ny, nz; 0: nothing)
     int64_t align_pts_n = -1;                                         //   (-1: nothing)
@@ -124,23 +121,18 @@ struct ptv_ctx {
     ptv::Event ev_edt0, ev_edt1;                                      // around the kernels of either
     ptv::DevBuf<double> spl_coef;                                     // map_coordinates: resident coefficients
     int64_t spl_dims[3] = {0, 0, 0};                                  //   what they hold (nx, ny, nz; 0: nothing)
-    ptv::DevBuf<uint8_t> spl_fld;                                     // its host calls: the field,
-    ptv::DevBuf<double> spl_pts, spl_out;                             //   coordinates, samples / coefficients
     ptv::DevBuf<double> mesh_coef[3];                                 // mesh drag: resident coefficients of U, V, W
     int64_t mesh_dims[3] = {0, 0, 0};                                 //   what they hold (nx, ny, nz; 0: nothing)
-    ptv::DevBuf<uint8_t> mesh_fld[4], mesh_bg, mesh_verts;            // its host calls: U, V, W, P, mask, vertices
-    int mesh_fld_dtype = -1;                                          //   what the resident fields are
-    bool mesh_has_p = false, mesh_has_bg = false;                     //   (-1: nothing)
+    ptv::DevBuf<uint8_t> mesh_fld[4], mesh_bg, mesh_verts;            // its host calls: U, V, W, P, mask, vertices,
+    int mesh_fld_dtype = -1;                                          //   resident for prm->reuse; what the fields
+    bool mesh_has_p = false, mesh_has_bg = false;                     //   are (-1: nothing)
     ptv::DevBuf<int32_t> mesh_faces, mesh_blk_label;                  // faces (host calls); block -> label slot
     ptv::DevBuf<int64_t> mesh_blk_first, mesh_lab_blk0, mesh_off;     // block -> first triangle; per-label tables
     ptv::DevBuf<double> mesh_part, mesh_res;                          // per-block partials, per-label sums
     ptv::Event ev_mesh[3];                                            // prefilter start, traction start, end
     ptv::SurfWork surf;                                               // marching cubes: scratch, the resident mesh
-    ptv::DevBuf<int32_t> surf_mask;                                   // its host calls: the mask
     ptv::Event ev_surf[3];                                            // counting start, emission start, end
     ptv::LabelWork label;                                             // component labelling: forest, flags, ranks
-    ptv::DevBuf<uint8_t> label_mask;                                  // its host calls: the mask
-    ptv::DevBuf<int32_t> label_out;                                   //   and the labels
     ptv::Event ev_label[3];                                           // start, after the border merge, end
     ptv::PinnedBuf<double> h_bbox;                                    // pinned, kHostWords doubles
     ptv::PinnedBuf<unsigned long long> h_misc;  // pinned scratch words (cull count, halo bound, repair count)
@@ -181,6 +173,17 @@ inline int launch_knn(const KnnLaunch &a, const Binned &b, const Queries &q, con
                       double *W, hipStream_t s) {
     return launch_knn(a, b, q.ax, q.ay, q.az, q.qx, q.qy, q.qz, mask, U, V, W, s);
 }
+
+// ---- ptv_api.cpp: what the host-buffer calls of every file share ----
+
+// The timings of the last call from its events, into c->last.
+int finish_timing(ptv_ctx *c);
+// finish_timing, and a host-buffer call's own legs: ev = call start, H2D end, D2H start, call end
+int finish_host_timing(ptv_ctx *c, const Event ev[4]);
+// The six particle columns -> the context's buffers; dp = the particles on the device.
+int upload_particles(ptv_ctx *c, const ptv_particles *p, hipStream_t s, ptv_particles &dp);
+// The grid's axes (separable) or point lists -> the context's buffers; dg = the grid on the device.
+int upload_grid(ptv_ctx *c, const ptv_grid *g, hipStream_t s, ptv_grid &dg);
 
 // ---- ptv_search.cpp ----
 

@@ -4,7 +4,7 @@
 
 #include <string>
 
-#include "ptv_ctx.hpp"
+#include "ptv_stage.hpp"
 
 using namespace ptv;
 
@@ -66,19 +66,19 @@ int ptv_label(ptv_ctx *c, const ptv_label_params *prm, const uint8_t *mask, int3
     LabelDims d{};
     PTV_TRY(label_args(c, prm, mask, labels, d));
     PTV_HIP(hipSetDevice(c->device));
-    hipStream_t s = c->stream;
+    Stage sg(c);
     const size_t n = (size_t)d.voxels();
-    PTV_TRY(c->label_mask.ensure(n));
-    PTV_TRY(c->label_out.ensure(n));
+    const uint8_t *dM = sg.in<uint8_t>(0, mask, n);
+    int32_t *dL = sg.room<int32_t>(1, n * sizeof(int32_t));
+    PTV_TRY(sg.rc);
     PTV_TRY(c->h_misc.ensure(kHostWords));
-    PTV_HIP(hipMemcpyAsync(c->label_mask.p, mask, n, hipMemcpyHostToDevice, s));
     int64_t nc = 0, nf = 0;
-    PTV_TRY(run_label(c->label, d, c->label_mask.p, c->label_out.p, nullptr, sizes != nullptr, s, c->ev_label,
-                      c->h_misc.p, &nc, &nf));
-    PTV_HIP(hipMemcpyAsync(labels, c->label_out.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    PTV_TRY(run_label(c->label, d, dM, dL, nullptr, sizes != nullptr, sg.s, c->ev_label, c->h_misc.p, &nc, &nf));
+    sg.back(labels, 1, n * sizeof(int32_t));
     if (sizes)
-        PTV_HIP(hipMemcpyAsync(sizes, c->label.sizes.p, ((size_t)nc + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    PTV_HIP(hipStreamSynchronize(s));
+        PTV_HIP(hipMemcpyAsync(sizes, c->label.sizes.p, ((size_t)nc + 1) * sizeof(int64_t), hipMemcpyDeviceToHost,
+                               sg.s));
+    PTV_TRY(sg.sync());
     return label_stats(c, nc, nf, st);
 }
 

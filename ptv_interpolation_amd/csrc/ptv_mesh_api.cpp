@@ -8,7 +8,7 @@
 #include <string>
 #include <vector>
 
-#include "ptv_ctx.hpp"
+#include "ptv_stage.hpp"
 
 using namespace ptv;
 
@@ -55,6 +55,30 @@ int elapsed(const Event &e0, const Event &e1, double *ms) {
     float t = 0.f;
     PTV_HIP(hipEventElapsedTime(&t, e0, e1));
     if (ms) *ms = t;
+    return PTV_OK;
+}
+
+int prefilter_args(ptv_ctx *c, const ptv_spline_params *prm, const void *field, const double *coef, SplineDims &d) {
+    PTV_TRY(spline_args(c, prm, "spline prefilter", d));
+    if (!field || !coef) {
+        set_error("spline prefilter: NULL field or coefficients");
+        return PTV_E_ARG;
+    }
+    return PTV_OK;
+}
+
+// what the host and the device call of map_coordinates check alike, before anything is copied
+int map_args(ptv_ctx *c, const ptv_spline_params *prm, const double *coords, const double *out, SplineDims &d,
+             bool device) {
+    PTV_TRY(spline_args(c, prm, "map_coordinates", d));
+    if (device && prm->order != 0 && prm->order != 1 && prm->order != 3) {
+        set_error("map_coordinates: order must be 0, 1 or 3");
+        return PTV_E_UNSUPPORTED;
+    }
+    if (prm->n_points < 0 || (prm->n_points > 0 && (!coords || !out))) {
+        set_error("map_coordinates: n_points >= 0 with their coordinates and output");
+        return PTV_E_ARG;
+    }
     return PTV_OK;
 }
 
@@ -143,11 +167,7 @@ extern "C" {
 int ptv_spline_prefilter_dev(ptv_ctx *c, const ptv_spline_params *prm, const void *field, double *coef, void *stream,
                              double *ms) {
     SplineDims d{};
-    PTV_TRY(spline_args(c, prm, "spline prefilter", d));
-    if (!field || !coef) {
-        set_error("spline prefilter: NULL field or coefficients");
-        return PTV_E_ARG;
-    }
+    PTV_TRY(prefilter_args(c, prm, field, coef, d));
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     PTV_TRY(c->ev_mesh[0].record(s));
     PTV_TRY(launch_spline_prefilter(d, field, prm->field_dtype == PTV_F32, coef, s));
@@ -158,33 +178,21 @@ int ptv_spline_prefilter_dev(ptv_ctx *c, const ptv_spline_params *prm, const voi
 
 int ptv_spline_prefilter(ptv_ctx *c, const ptv_spline_params *prm, const void *field, double *coef, double *ms) {
     SplineDims d{};
-    PTV_TRY(spline_args(c, prm, "spline prefilter", d));
-    if (!field || !coef) {
-        set_error("spline prefilter: NULL field or coefficients");
-        return PTV_E_ARG;
-    }
-    hipStream_t s = c->stream;
+    PTV_TRY(prefilter_args(c, prm, field, coef, d));
+    Stage sg(c);
     const size_t bytes = (size_t)d.nx * d.ny * d.nz * (prm->field_dtype == PTV_F32 ? 4 : 8);
-    PTV_TRY(c->spl_fld.ensure(bytes));
-    PTV_TRY(c->spl_out.ensure(d.padded()));
-    PTV_HIP(hipMemcpyAsync(c->spl_fld.p, field, bytes, hipMemcpyHostToDevice, s));
-    PTV_TRY(ptv_spline_prefilter_dev(c, prm, c->spl_fld.p, c->spl_out.p, s, ms));
-    PTV_HIP(hipMemcpy(coef, c->spl_out.p, d.padded() * sizeof(double), hipMemcpyDeviceToHost));
+    const void *dF = sg.in(0, field, bytes);
+    double *dC = sg.room<double>(1, d.padded() * sizeof(double));
+    PTV_TRY(sg.rc);
+    PTV_TRY(ptv_spline_prefilter_dev(c, prm, dF, dC, sg.s, ms));
+    PTV_HIP(hipMemcpy(coef, dC, d.padded() * sizeof(double), hipMemcpyDeviceToHost));  // synchronised by the device call
     return PTV_OK;
 }
 
 int ptv_map_coordinates_dev(ptv_ctx *c, const ptv_spline_params *prm, const void *field, const double *coords,
                             double *out, void *stream, double *ms) {
     SplineDims d{};
-    PTV_TRY(spline_args(c, prm, "map_coordinates", d));
-    if (prm->order != 0 && prm->order != 1 && prm->order != 3) {
-        set_error("map_coordinates: order must be 0, 1 or 3");
-        return PTV_E_UNSUPPORTED;
-    }
-    if (prm->n_points < 0 || (prm->n_points > 0 && (!coords || !out))) {
-        set_error("map_coordinates: n_points >= 0 with their coordinates and output");
-        return PTV_E_ARG;
-    }
+    PTV_TRY(map_args(c, prm, coords, out, d, true));
     if (!field && prm->order != 3) {
         set_error("map_coordinates: orders 0 and 1 read the field (NULL)");
         return PTV_E_ARG;
@@ -217,23 +225,16 @@ int ptv_map_coordinates_dev(ptv_ctx *c, const ptv_spline_params *prm, const void
 int ptv_map_coordinates(ptv_ctx *c, const ptv_spline_params *prm, const void *field, const double *coords, double *out,
                         double *ms) {
     SplineDims d{};
-    PTV_TRY(spline_args(c, prm, "map_coordinates", d));
-    if (prm->n_points < 0 || (prm->n_points > 0 && (!coords || !out))) {
-        set_error("map_coordinates: n_points >= 0 with their coordinates and output");
-        return PTV_E_ARG;
-    }
-    hipStream_t s = c->stream;
+    PTV_TRY(map_args(c, prm, coords, out, d, false));  // the order is checked after the upload
+    Stage sg(c);
     const size_t n = (size_t)prm->n_points;
-    if (field) {
-        const size_t bytes = (size_t)d.nx * d.ny * d.nz * (prm->field_dtype == PTV_F32 ? 4 : 8);
-        PTV_TRY(c->spl_fld.ensure(bytes));
-        PTV_HIP(hipMemcpyAsync(c->spl_fld.p, field, bytes, hipMemcpyHostToDevice, s));
-    }
-    PTV_TRY(c->spl_pts.ensure(3 * n));
-    PTV_TRY(c->spl_out.ensure(n));
-    if (n) PTV_HIP(hipMemcpyAsync(c->spl_pts.p, coords, 3 * n * sizeof(double), hipMemcpyHostToDevice, s));
-    PTV_TRY(ptv_map_coordinates_dev(c, prm, field ? c->spl_fld.p : nullptr, c->spl_pts.p, c->spl_out.p, s, ms));
-    if (n) PTV_HIP(hipMemcpy(out, c->spl_out.p, n * sizeof(double), hipMemcpyDeviceToHost));
+    const size_t bytes = (size_t)d.nx * d.ny * d.nz * (prm->field_dtype == PTV_F32 ? 4 : 8);
+    const void *dF = field ? sg.in(0, field, bytes) : nullptr;
+    const double *dX = n ? sg.in<double>(1, coords, 3 * n * sizeof(double)) : sg.room<double>(1, 0);
+    double *dO = sg.room<double>(2, n * sizeof(double));
+    PTV_TRY(sg.rc);
+    PTV_TRY(ptv_map_coordinates_dev(c, prm, dF, dX, dO, sg.s, ms));
+    if (n) PTV_HIP(hipMemcpy(out, dO, n * sizeof(double), hipMemcpyDeviceToHost));  // synchronised by the device call
     return PTV_OK;
 }
 

@@ -478,7 +478,7 @@ __global__ __launch_bounds__(kGridFinalThreads) void k_pcg_scalar(int phase, CgC
     }
 }
 
-int make_args(const PressGrid &g, PArgs &a) {
+int make_args(const GridSpec &g, PArgs &a) {
     PTV_TRY(grid_dims("pressure", g.nx, g.ny, g.nz, a));
     if (!(g.dx > 0.0) || !(g.dy > 0.0) || !(g.dz > 0.0) || !std::isfinite(g.dx) || !std::isfinite(g.dy) ||
         !std::isfinite(g.dz)) {
@@ -502,7 +502,7 @@ int scalar(PressWork &wk, int phase, const CgCfg &cfg, unsigned nb, hipStream_t 
 
 }  // namespace
 
-int press_force(PressWork &wk, const PressGrid &g, double mu, double rho, const uint8_t *M, const double *U,
+int press_force(PressWork &wk, const GridSpec &g, double mu, double rho, const uint8_t *M, const double *U,
                 const double *V, const double *W, double *Fx, double *Fy, double *Fz, hipStream_t s,
                 ptv_pressure_stats *st) {
     PArgs a{};
@@ -553,7 +553,7 @@ int press_force(PressWork &wk, const PressGrid &g, double mu, double rho, const 
     return PTV_OK;
 }
 
-int press_divergence(const PressGrid &g, bool inhomogeneous, const uint8_t *M, const double *Fx, const double *Fy,
+int press_divergence(const GridSpec &g, bool inhomogeneous, const uint8_t *M, const double *Fx, const double *Fy,
                      const double *Fz, double *D, hipStream_t s) {
     PArgs a{};
     PTV_TRY(make_args(g, a));
@@ -563,7 +563,7 @@ int press_divergence(const PressGrid &g, bool inhomogeneous, const uint8_t *M, c
     return PTV_OK;
 }
 
-int press_anchor_plane(const PressGrid &g, int z, const uint8_t *M, uint8_t *Dir, hipStream_t s) {
+int press_anchor_plane(const GridSpec &g, int z, const uint8_t *M, uint8_t *Dir, hipStream_t s) {
     PArgs a{};
     PTV_TRY(make_args(g, a));
     if (z < 0 || z >= a.nz) {
@@ -576,7 +576,7 @@ int press_anchor_plane(const PressGrid &g, int z, const uint8_t *M, uint8_t *Dir
     return PTV_OK;
 }
 
-int press_cg(PressWork &wk, const PressGrid &g, double rtol, int maxiter, const uint8_t *M, const uint8_t *Dir,
+int press_cg(PressWork &wk, const GridSpec &g, double rtol, int maxiter, const uint8_t *M, const uint8_t *Dir,
              const double *B, double *X, hipStream_t s, ptv_pressure_stats *st) {
     PArgs a{};
     PTV_TRY(make_args(g, a));

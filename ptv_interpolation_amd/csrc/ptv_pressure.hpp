@@ -11,11 +11,6 @@
 
 namespace ptv {
 
-struct PressGrid {
-    int nx, ny, nz;
-    double dx, dy, dz;
-};
-
 // grow-only device scratch of the pressure recovery, owned by the context
 struct PressWork {
     DevBuf<double> lap;            // the three Laplacians (raw, then filled in place)
@@ -31,17 +26,17 @@ struct PressWork {
 
 // All pointers device memory.  The force field's sums over the fluid voxels land in st (sum_abs_f*,
 // sum_w, n_fluid); F must not alias U, V, W.  Synchronises `s`.
-int press_force(PressWork &wk, const PressGrid &g, double mu, double rho, const uint8_t *M, const double *U,
+int press_force(PressWork &wk, const GridSpec &g, double mu, double rho, const uint8_t *M, const double *U,
                 const double *V, const double *W, double *Fx, double *Fy, double *Fz, hipStream_t s,
                 ptv_pressure_stats *st);
 // D = the force divergence at every voxel; D must not alias F.
-int press_divergence(const PressGrid &g, bool inhomogeneous, const uint8_t *M, const double *Fx, const double *Fy,
+int press_divergence(const GridSpec &g, bool inhomogeneous, const uint8_t *M, const double *Fx, const double *Fy,
                      const double *Fz, double *D, hipStream_t s);
 // scipy's cg(A, b, rtol, atol=0, maxiter) on the Laplacian with the Dirichlet rows and columns
 // eliminated; Dir may be NULL (no Dirichlet voxel), X may alias B.  Synchronises `s`.
-int press_cg(PressWork &wk, const PressGrid &g, double rtol, int maxiter, const uint8_t *M, const uint8_t *Dir,
+int press_cg(PressWork &wk, const GridSpec &g, double rtol, int maxiter, const uint8_t *M, const uint8_t *Dir,
              const double *B, double *X, hipStream_t s, ptv_pressure_stats *st);
 // Dir[i] = M[i] != 0 on plane z, 0 elsewhere
-int press_anchor_plane(const PressGrid &g, int z, const uint8_t *M, uint8_t *Dir, hipStream_t s);
+int press_anchor_plane(const GridSpec &g, int z, const uint8_t *M, uint8_t *Dir, hipStream_t s);
 
 }  // namespace ptv

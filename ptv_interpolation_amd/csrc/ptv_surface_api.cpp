@@ -6,7 +6,7 @@
 #include <string>
 #include <vector>
 
-#include "ptv_ctx.hpp"
+#include "ptv_stage.hpp"
 
 using namespace ptv;
 
@@ -103,9 +103,10 @@ int ptv_marching_cubes(ptv_ctx *c, const ptv_surface_params *prm, const int32_t 
         return PTV_E_ARG;
     }
     const size_t n = (size_t)prm->nx * (size_t)prm->ny * (size_t)prm->nz;
-    PTV_TRY(c->surf_mask.ensure(n));
-    PTV_HIP(hipMemcpyAsync(c->surf_mask.p, mask, n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    return ptv_marching_cubes_dev(c, prm, c->surf_mask.p, c->stream, vert_counts, tri_counts, ms2);
+    Stage sg(c);
+    const int32_t *dM = sg.in<int32_t>(0, mask, n * sizeof(int32_t));
+    PTV_TRY(sg.rc);
+    return ptv_marching_cubes_dev(c, prm, dM, sg.s, vert_counts, tri_counts, ms2);
 }
 
 int ptv_surface_fetch(ptv_ctx *c, float *verts, int32_t *faces) {

@@ -381,7 +381,7 @@ __global__ __launch_bounds__(kGridFinalThreads) void k_cg_scalar(int phase, CgCf
     }
 }
 
-int make_args(const VarGrid &g, double lambda_reg, VarArgs &a) {
+int make_args(const GridSpec &g, double lambda_reg, VarArgs &a) {
     PTV_TRY(grid_dims("variational", g.nx, g.ny, g.nz, a));
     if (!(g.dx > 0.0) || !(g.dy > 0.0) || !(g.dz > 0.0) || !std::isfinite(g.dx) || !std::isfinite(g.dy) ||
         !std::isfinite(g.dz)) {
@@ -407,7 +407,7 @@ int make_args(const VarGrid &g, double lambda_reg, VarArgs &a) {
 
 }  // namespace
 
-int launch_var_divergence(const VarGrid &g, const uint8_t *M, const double *xu, const double *xv, const double *xw,
+int launch_var_divergence(const GridSpec &g, const uint8_t *M, const double *xu, const double *xv, const double *xw,
                           double *d, hipStream_t s) {
     VarArgs a{};
     PTV_TRY(make_args(g, 0.0, a));
@@ -417,7 +417,7 @@ int launch_var_divergence(const VarGrid &g, const uint8_t *M, const double *xu, 
     return PTV_OK;
 }
 
-int launch_var_adjoint(const VarGrid &g, double lambda_reg, const uint8_t *M, const double *d, const double *xu,
+int launch_var_adjoint(const GridSpec &g, double lambda_reg, const uint8_t *M, const double *d, const double *xu,
                        const double *xv, const double *xw, double *yu, double *yv, double *yw, DevBuf<double> &part,
                        hipStream_t s) {
     VarArgs a{};
@@ -429,7 +429,7 @@ int launch_var_adjoint(const VarGrid &g, double lambda_reg, const uint8_t *M, co
     return PTV_OK;
 }
 
-int variational_run(VarWork &wk, const VarGrid &g, const VarSolve &sv, const uint8_t *M, const double *U,
+int variational_run(VarWork &wk, const GridSpec &g, const VarSolve &sv, const uint8_t *M, const double *U,
                     const double *V, const double *W, double *Uo, double *Vo, double *Wo, hipStream_t s,
                     ptv_variational_stats *st) {
     VarArgs a{};

@@ -11,11 +11,6 @@
 
 namespace ptv {
 
-struct VarGrid {
-    int nx, ny, nz;
-    double dx, dy, dz;
-};
-
 // grow-only device scratch of the CG solve, owned by the context
 struct VarWork {
     DevBuf<double> x, r, p[2], q;  // CG vectors: three dense grids each (u, v, w parts); p ping-pongs
@@ -33,14 +28,14 @@ struct VarSolve {
 };
 
 // all pointers device memory; Uo, Vo, Wo may alias U, V, W.  Synchronises `s`.
-int variational_run(VarWork &wk, const VarGrid &g, const VarSolve &sv, const uint8_t *M, const double *U,
+int variational_run(VarWork &wk, const GridSpec &g, const VarSolve &sv, const uint8_t *M, const double *U,
                     const double *V, const double *W, double *Uo, double *Vo, double *Wo, hipStream_t s,
                     ptv_variational_stats *st);
 // d = Dx xu + Dy xv + Dz xw (solid voxels written as 0)
-int launch_var_divergence(const VarGrid &g, const uint8_t *M, const double *xu, const double *xv, const double *xw,
+int launch_var_divergence(const GridSpec &g, const uint8_t *M, const double *xu, const double *xv, const double *xw,
                           double *d, hipStream_t s);
 // y = x + lambda D^T d on the three parts (solid voxels written as 0); `part` holds one double per block
-int launch_var_adjoint(const VarGrid &g, double lambda_reg, const uint8_t *M, const double *d, const double *xu,
+int launch_var_adjoint(const GridSpec &g, double lambda_reg, const uint8_t *M, const double *d, const double *xu,
                        const double *xv, const double *xw, double *yu, double *yv, double *yw, DevBuf<double> &part,
                        hipStream_t s);
 

@@ -50,6 +50,24 @@ def _one_cycle():
                                                  [11.0] * 3)
         assert len(out["boundary"][0]) > 0
         out["clean"], _ = ctx.clean_divergence(*f, fluid, 1.0, 1.0, 1.0, iterations=2)
+        out["variational"], _ = ctx.clean_variational(*f, fluid, 1.0, 1.0, 1.0, lambda_reg=200.0, maxiter=20)
+        out["pressure"] = (ctx.pressure_recover(*f, fluid, 1.0, 1.0, 1.0, 1e-3, maxiter=20)[0],)
+        flow, _ = ctx.flow_analysis(*f, 1.0, 1.0, 1.0, viscosity=1e-3, fluid_mask=fluid)
+        out["flow"] = tuple(flow[name] for name in _lib.FLOW_OUTPUTS)
+        grains = rng.integers(0, 3, (12, 12, 12)).astype(np.int32)
+        as_bytes = lambda rec: np.frombuffer(rec.tobytes(), dtype=np.uint8)  # noqa: E731  (record arrays)
+        out["drag"] = (as_bytes(ctx.interface_drag(grains, *f, None, 1e-3, 1.0, 1.0, 1.0, [1, 2])[0]),)
+        d2, dist, _ = ctx.edt(fluid.view(np.uint8), keep_distance=True)
+        out["edt"] = (d2, dist)
+        out["align"] = (as_bytes(ctx.align_score((12, 12, 12), 30, rng.standard_normal((4, 3)),
+                                                 points=rng.random((30, 3)) * 11.0)[0]),)  # against the kept field
+        coords = rng.random((3, 25)) * 11.0
+        out["spline"] = (ctx.spline_prefilter(f[0])[0], ctx.map_coordinates(f[0], coords)[0],
+                         ctx.map_coordinates(None, coords, shape=(12, 12, 12))[0])  # the resident coefficients
+        labels, sizes, _ = ctx.label(fluid.view(np.uint8), connectivity=26, want_sizes=True)
+        out["label"] = (labels, sizes)
+        nv, nt, _ = ctx.marching_cubes(grains, [1, 2])
+        out["marching cubes"] = (nv, nt) + tuple(a for pair in ctx.surface_fetch(nv, nt) for a in pair)
     finally:
         ctx.close()
     ctx.close()  # already closed
