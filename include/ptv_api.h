@@ -498,6 +498,33 @@ typedef struct {
 } ptv_pressure_stats;
 
 /*
+ * Multigrid-preconditioned CG for the anchored Poisson solve (scipy's cg(A, b, M=...), DESIGN.md
+ * section 25).  M is one symmetric V-cycle on the active (fluid, not Dirichlet) voxels: levels of
+ * ceil(n / 2) cells per axis by piecewise-constant aggregation of 2 x 2 x 2 cells until every extent is
+ * at most 2 (or max_levels levels exist), exact Galerkin operators, nu damped-Jacobi sweeps before and
+ * after the coarse correction, coarse_sweeps sweeps on the coarsest level.  Every operation is
+ * elementwise or a sum of at most eight terms in a stated order, so z = M r is the same bits as the
+ * numpy restatement's.  Opt-in: no existing entry point changes.
+ * PTV_API_VERSION is not raised: the presence of ptv_abi_sizes13 is the capability probe.
+ */
+#define PTV_MG_MAX_LEVELS 32
+typedef struct {
+    int max_levels;    /* >= 0; 0: as many as the coarsening rule gives */
+    int nu;            /* >= 0; 0: 2 sweeps before and 2 after */
+    int coarse_sweeps; /* >= 0; 0: 16 */
+    double omega;      /* finite, >= 0; 0: 2/3 */
+} ptv_mg_params;
+
+typedef struct {
+    int32_t levels;     /* levels built, level 0 (the grid) included */
+    int32_t tail_level; /* the first level that runs inside the one-workgroup launch */
+    int64_t cells[PTV_MG_MAX_LEVELS];  /* per level */
+    int64_t active[PTV_MG_MAX_LEVELS]; /* per level: cells with a non-zero diagonal (the cells a sweep moves) */
+    double ms_setup;                   /* the coarse operators, hipEvent based */
+    double ms_vcycle_median;           /* median ms of the V-cycles timed (one per polling batch; the one of an apply) */
+} ptv_mg_stats;
+
+/*
  * Cubic B-spline sampling and the mesh interface drag (scipy.ndimage.spline_filter and
  * map_coordinates with mode='nearest'; velocity_analysis.compute_interface_drag_mesh from the
  * triangulation onward, velocity_analysis.py:547-655).  Fields are (nz, ny, nx) C order.
@@ -654,6 +681,9 @@ int ptv_abi_sizes11(int64_t out1[1]);
 /* sizeof(ptv_label_params, ptv_label_stats): the same self-check.  A library that has this symbol has
  * the component labelling entry points (PTV_API_VERSION stays 11). */
 int ptv_abi_sizes12(int64_t out2[2]);
+/* sizeof(ptv_mg_params, ptv_mg_stats): the same self-check.  A library that has this symbol has the
+ * multigrid-preconditioned Poisson entry points (PTV_API_VERSION stays 11). */
+int ptv_abi_sizes13(int64_t out2[2]);
 const char *ptv_last_error(void);
 int ptv_device_count(int *out);
 int ptv_init(int device, ptv_ctx **out);
@@ -968,6 +998,48 @@ int ptv_pressure_recover(ptv_ctx *ctx, const ptv_pressure_params *prm, const dou
 /* Same on device pointers, enqueued on `stream`; synchronises.  P may alias none of the inputs. */
 int ptv_pressure_recover_dev(ptv_ctx *ctx, const ptv_pressure_params *prm, const double *U, const double *V,
                              const double *W, double *P, void *stream, ptv_pressure_stats *st);
+
+/*
+ * z = M r, host buffers: one V-cycle of the multigrid preconditioner for the mask, the Dirichlet grid
+ * (may be NULL: no Dirichlet voxel) and the spacings of prm; mg may be NULL (the defaults).  r is read
+ * at active voxels only; z is 0 at every other voxel.  Of prm only nx, ny, nz, dx, dy, dz and
+ * fluid_mask are read.  mst (may be NULL) receives the hierarchy, ms_setup and the V-cycle's time.
+ */
+int ptv_poisson_mg_apply(ptv_ctx *ctx, const ptv_pressure_params *prm, const ptv_mg_params *mg,
+                         const uint8_t *dirichlet, const double *r, double *z, ptv_mg_stats *mst);
+
+/* Same on device pointers, enqueued on `stream`; synchronises.  z must not alias r. */
+int ptv_poisson_mg_apply_dev(ptv_ctx *ctx, const ptv_pressure_params *prm, const ptv_mg_params *mg,
+                             const uint8_t *dirichlet, const double *r, double *z, void *stream,
+                             ptv_mg_stats *mst);
+
+/*
+ * ptv_poisson_solve with scipy's preconditioned recurrence, cg(A, b, M=V-cycle, rtol, atol=0,
+ * maxiter): the same right-hand side, outputs, stopping rules and NaN outcome.  The Dirichlet grid is
+ * required: NULL (the LSQR branch) returns PTV_E_UNSUPPORTED.  mg may be NULL (the defaults); mst may
+ * be NULL.
+ */
+int ptv_poisson_solve_mg(ptv_ctx *ctx, const ptv_pressure_params *prm, const double *rhs, const double *Fx,
+                         const double *Fy, const double *Fz, const uint8_t *dirichlet, double *X,
+                         const ptv_mg_params *mg, ptv_pressure_stats *st, ptv_mg_stats *mst);
+
+/* Same on device pointers, enqueued on `stream`; synchronises.  X may alias rhs. */
+int ptv_poisson_solve_mg_dev(ptv_ctx *ctx, const ptv_pressure_params *prm, const double *rhs, const double *Fx,
+                             const double *Fy, const double *Fz, const uint8_t *dirichlet, double *X, void *stream,
+                             const ptv_mg_params *mg, ptv_pressure_stats *st, ptv_mg_stats *mst);
+
+/*
+ * The chain of ptv_pressure_recover with the anchored solve preconditioned.  prm->anchor ==
+ * PTV_ANCHOR_NONE (the LSQR solve) returns PTV_E_UNSUPPORTED before anything is written.
+ */
+int ptv_pressure_recover_mg(ptv_ctx *ctx, const ptv_pressure_params *prm, const double *U, const double *V,
+                            const double *W, double *P, const ptv_mg_params *mg, ptv_pressure_stats *st,
+                            ptv_mg_stats *mst);
+
+/* Same on device pointers, enqueued on `stream`; synchronises.  P may alias none of the inputs. */
+int ptv_pressure_recover_mg_dev(ptv_ctx *ctx, const ptv_pressure_params *prm, const double *U, const double *V,
+                                const double *W, double *P, void *stream, const ptv_mg_params *mg,
+                                ptv_pressure_stats *st, ptv_mg_stats *mst);
 
 /*
  * Cubic B-spline prefilter, host buffers: H2D of the field, the three passes, D2H of the

@@ -244,6 +244,35 @@ class PressureStats(C.Structure):
         return {f: getattr(self, f) for f, _ in self._fields_}
 
 
+MG_MAX_LEVELS = 32  # PTV_MG_MAX_LEVELS
+
+
+class MgParams(C.Structure):
+    """The multigrid preconditioner's parameters; a zero means the default (2, 16, 2/3, no cap)."""
+    _fields_ = [("max_levels", C.c_int), ("nu", C.c_int), ("coarse_sweeps", C.c_int), ("omega", C.c_double)]
+
+
+class MgStats(C.Structure):
+    _fields_ = [("levels", C.c_int32), ("tail_level", C.c_int32), ("cells", C.c_int64 * MG_MAX_LEVELS),
+                ("active", C.c_int64 * MG_MAX_LEVELS), ("ms_setup", C.c_double), ("ms_vcycle_median", C.c_double)]
+
+    def as_dict(self):
+        n = int(self.levels)
+        return {"levels": n, "tail_level": int(self.tail_level), "cells": list(self.cells)[:n],
+                "active": list(self.active)[:n], "ms_setup": self.ms_setup,
+                "ms_vcycle_median": self.ms_vcycle_median}
+
+
+def mg_params(multigrid=None):
+    """``multigrid``: None or a dict with any of max_levels, nu, coarse_sweeps, omega."""
+    kw = dict(multigrid or {})
+    prm = MgParams(int(kw.pop("max_levels", 0)), int(kw.pop("nu", 0)), int(kw.pop("coarse_sweeps", 0)),
+                   float(kw.pop("omega", 0.0)))
+    if kw:
+        raise ValueError(f"unknown multigrid parameters {sorted(kw)} (max_levels, nu, coarse_sweeps, omega)")
+    return prm
+
+
 class EdtParams(C.Structure):
     _fields_ = [("nx", C.c_int64), ("ny", C.c_int64), ("nz", C.c_int64), ("keep_distance", C.c_int)]
 
@@ -397,6 +426,20 @@ EXPORTS = {
     "ptv_abi_sizes12": (C.c_int, [C.POINTER(C.c_int64)]),
     "ptv_label": (C.c_int, [C.c_void_p, C.POINTER(LabelParams)] + [C.c_void_p] * 3 + [C.POINTER(LabelStats)]),
     "ptv_label_dev": (C.c_int, [C.c_void_p, C.POINTER(LabelParams)] + [C.c_void_p] * 4 + [C.POINTER(LabelStats)]),
+    "ptv_abi_sizes13": (C.c_int, [C.POINTER(C.c_int64)]),
+    "ptv_poisson_mg_apply": (C.c_int, [C.c_void_p, C.POINTER(PressureParams), C.POINTER(MgParams), _u8p, _dp, _dp,
+                                       C.POINTER(MgStats)]),
+    "ptv_poisson_mg_apply_dev": (C.c_int, [C.c_void_p, C.POINTER(PressureParams), C.POINTER(MgParams), _u8p, _dp, _dp,
+                                           C.c_void_p, C.POINTER(MgStats)]),
+    "ptv_poisson_solve_mg": (C.c_int, [C.c_void_p, C.POINTER(PressureParams)] + [_dp] * 4 +
+                             [_u8p, _dp, C.POINTER(MgParams), C.POINTER(PressureStats), C.POINTER(MgStats)]),
+    "ptv_poisson_solve_mg_dev": (C.c_int, [C.c_void_p, C.POINTER(PressureParams)] + [_dp] * 4 +
+                                 [_u8p, _dp, C.c_void_p, C.POINTER(MgParams), C.POINTER(PressureStats),
+                                  C.POINTER(MgStats)]),
+    "ptv_pressure_recover_mg": (C.c_int, [C.c_void_p, C.POINTER(PressureParams)] + [_dp] * 4 +
+                                [C.POINTER(MgParams), C.POINTER(PressureStats), C.POINTER(MgStats)]),
+    "ptv_pressure_recover_mg_dev": (C.c_int, [C.c_void_p, C.POINTER(PressureParams)] + [_dp] * 4 +
+                                    [C.c_void_p, C.POINTER(MgParams), C.POINTER(PressureStats), C.POINTER(MgStats)]),
     "ptv_last_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     "ptv_debug_stamps": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double)]),
 }
@@ -548,6 +591,13 @@ def abi_sizes12():
     out = (C.c_int64 * 2)()
     check(lib().ptv_abi_sizes12(out))
     return list(out), [C.sizeof(LabelParams), C.sizeof(LabelStats)]
+
+
+def abi_sizes13():
+    """(C sizeof, ctypes sizeof) of ptv_mg_params and ptv_mg_stats."""
+    out = (C.c_int64 * 2)()
+    check(lib().ptv_abi_sizes13(out))
+    return list(out), [C.sizeof(MgParams), C.sizeof(MgStats)]
 
 
 def label_check_shape(shape):
@@ -1401,6 +1451,97 @@ class Context:
         check(lib().ptv_pressure_recover_dev(self.h, C.byref(prm), *[dev_dp(p) for p in ptrs], dev_dp(out_ptr),
                                              C.c_void_p(stream or 0), C.byref(st)))
         return st.as_dict()
+
+    # -- the anchored solve with the multigrid preconditioner ----
+    @staticmethod
+    def _with_mg(st, mst):
+        d = st.as_dict()
+        d["multigrid"] = mst.as_dict()
+        return d
+
+    def poisson_mg_apply(self, fluid_mask, dx, dy, dz, r, dirichlet=None, multigrid=None):
+        """``z = M r``: one V-cycle of the preconditioner for host arrays.  Returns ``(z, multigrid stats)``."""
+        r = np.ascontiguousarray(r, dtype=np.float64)
+        mk = self._mask_bytes(fluid_mask, r.shape)
+        dm = self._mask_bytes(dirichlet, r.shape) if dirichlet is not None else None
+        prm = self._pressure_params(r.shape, mk.ctypes.data, dx, dy, dz)
+        mg = mg_params(multigrid)
+        z = np.empty_like(r)
+        mst = MgStats()
+        check(lib().ptv_poisson_mg_apply(self.h, C.byref(prm), C.byref(mg),
+                                         dm.ctypes.data_as(_u8p) if dm is not None else None, as_dp(r), as_dp(z),
+                                         C.byref(mst)))
+        return z, mst.as_dict()
+
+    def poisson_mg_apply_dev(self, nx, ny, nz, mask_ptr, r_ptr, z_ptr, dx, dy, dz, dirichlet_ptr=0, multigrid=None,
+                             stream=0):
+        """Device-pointer V-cycle (``z_ptr`` must not be ``r_ptr``); returns the multigrid stats."""
+        prm = self._pressure_params((nz, ny, nx), mask_ptr, dx, dy, dz)
+        mg = mg_params(multigrid)
+        mst = MgStats()
+        check(lib().ptv_poisson_mg_apply_dev(self.h, C.byref(prm), C.byref(mg),
+                                             C.cast(C.c_void_p(dirichlet_ptr), _u8p) if dirichlet_ptr else None,
+                                             dev_dp(r_ptr), dev_dp(z_ptr), C.c_void_p(stream or 0), C.byref(mst)))
+        return mst.as_dict()
+
+    def poisson_solve_mg(self, fluid_mask, dx, dy, dz, rhs=None, force_field=None, dirichlet=None,
+                         wall_bc="inhomogeneous", multigrid=None, **solver):
+        """``poisson_solve`` with scipy's preconditioned recurrence, M = the V-cycle; ``dirichlet`` is
+        required (``NotImplementedError`` without).  The stats carry a ``multigrid`` dict."""
+        src = [rhs] if rhs is not None else list(force_field)
+        src = [np.ascontiguousarray(a, dtype=np.float64) for a in src]
+        shape = src[0].shape
+        mk = self._mask_bytes(fluid_mask, shape)
+        dm = self._mask_bytes(dirichlet, shape) if dirichlet is not None else None
+        prm = self._pressure_params(shape, mk.ctypes.data, dx, dy, dz, wall_bc=wall_bc, **solver)
+        mg = mg_params(multigrid)
+        x = np.empty(shape, dtype=np.float64)
+        st, mst = PressureStats(), MgStats()
+        ptrs = [as_dp(src[0]), None, None, None] if rhs is not None else [None] + [as_dp(a) for a in src]
+        check(lib().ptv_poisson_solve_mg(self.h, C.byref(prm), *ptrs,
+                                         dm.ctypes.data_as(_u8p) if dm is not None else None, as_dp(x), C.byref(mg),
+                                         C.byref(st), C.byref(mst)))
+        return x, self._with_mg(st, mst)
+
+    def poisson_solve_mg_dev(self, nx, ny, nz, mask_ptr, out_ptr, dx, dy, dz, rhs_ptr=0, force_ptrs=None,
+                             dirichlet_ptr=0, wall_bc="inhomogeneous", multigrid=None, stream=0, **solver):
+        """Device-pointer preconditioned solve (``out_ptr`` may be ``rhs_ptr``); returns the stats dict."""
+        prm = self._pressure_params((nz, ny, nx), mask_ptr, dx, dy, dz, wall_bc=wall_bc, **solver)
+        mg = mg_params(multigrid)
+        st, mst = PressureStats(), MgStats()
+        ptrs = [dev_dp(rhs_ptr) if rhs_ptr else None] + [dev_dp(p) if p else None for p in (force_ptrs or (0, 0, 0))]
+        check(lib().ptv_poisson_solve_mg_dev(self.h, C.byref(prm), *ptrs,
+                                             C.cast(C.c_void_p(dirichlet_ptr), _u8p) if dirichlet_ptr else None,
+                                             dev_dp(out_ptr), C.c_void_p(stream or 0), C.byref(mg), C.byref(st),
+                                             C.byref(mst)))
+        return self._with_mg(st, mst)
+
+    def pressure_recover_mg(self, u, v, w, fluid_mask, dx, dy, dz, mu, rho=0.0, wall_bc="zero-neumann",
+                            anchor="outlet", flow_direction="auto", multigrid=None, **solver):
+        """``pressure_recover`` with the anchored solve preconditioned (``anchor='none'`` raises
+        ``NotImplementedError``).  Returns ``(p, stats dict)``."""
+        f = [np.ascontiguousarray(a, dtype=np.float64) for a in (u, v, w)]
+        mk = self._mask_bytes(fluid_mask, f[0].shape)
+        prm = self._pressure_params(f[0].shape, mk.ctypes.data, dx, dy, dz, mu, rho, wall_bc, anchor, flow_direction,
+                                    **solver)
+        mg = mg_params(multigrid)
+        p = np.empty_like(f[0])
+        st, mst = PressureStats(), MgStats()
+        check(lib().ptv_pressure_recover_mg(self.h, C.byref(prm), *[as_dp(a) for a in f], as_dp(p), C.byref(mg),
+                                            C.byref(st), C.byref(mst)))
+        return p, self._with_mg(st, mst)
+
+    def pressure_recover_mg_dev(self, nx, ny, nz, ptrs, mask_ptr, out_ptr, dx, dy, dz, mu, rho=0.0,
+                                wall_bc="zero-neumann", anchor="outlet", flow_direction="auto", multigrid=None,
+                                stream=0, **solver):
+        """Device-pointer chain with the anchored solve preconditioned; returns the stats dict."""
+        prm = self._pressure_params((nz, ny, nx), mask_ptr, dx, dy, dz, mu, rho, wall_bc, anchor, flow_direction,
+                                    **solver)
+        mg = mg_params(multigrid)
+        st, mst = PressureStats(), MgStats()
+        check(lib().ptv_pressure_recover_mg_dev(self.h, C.byref(prm), *[dev_dp(p) for p in ptrs], dev_dp(out_ptr),
+                                                C.c_void_p(stream or 0), C.byref(mg), C.byref(st), C.byref(mst)))
+        return self._with_mg(st, mst)
 
     # -- distance transform and alignment score (auto_align.py:10-62) ----
     def edt(self, mask, want_d2=True, want_distance=True, keep_distance=False):

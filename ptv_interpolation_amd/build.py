@@ -26,7 +26,7 @@ SOURCES = (["ptv_api.cpp", "ptv_search.cpp", "ptv_run_knn.cpp", "ptv_run_chunked
             "ptv_surface_api.cpp", "ptv_surface.hip", "ptv_label_api.cpp", "ptv_label.hip",
             "ptv_bin.hip", "ptv_knn.hip"] + KNN_PARTS +
            ["ptv_rbf.hip"] + ["ptv_rbf_ns_" + g + ".hip" for g in "abcd"] +
-           ["ptv_div.hip", "ptv_flow.hip", "ptv_drag.hip", "ptv_edt.hip", "ptv_clean.hip", "ptv_variational.hip", "ptv_pressure.hip", "ptv_mask.hip", "ptv_filter.hip", "ptv_linear.hip", "ptv_knn_big.hip"])
+           ["ptv_div.hip", "ptv_flow.hip", "ptv_drag.hip", "ptv_edt.hip", "ptv_clean.hip", "ptv_variational.hip", "ptv_pressure.hip", "ptv_multigrid.hip", "ptv_mask.hip", "ptv_filter.hip", "ptv_linear.hip", "ptv_knn_big.hip"])
 ARCH = os.environ.get("PTV_OFFLOAD_ARCH", "gfx950")
 # per-file extras: the local-RBF kernel keeps each voxel's system row in registers, so every
 # loop over the row must unroll fully (a partial unroll turns the row into scratch memory)

@@ -161,6 +161,16 @@ int ptv_abi_sizes12(int64_t out2[2]) {
     return PTV_OK;
 }
 
+int ptv_abi_sizes13(int64_t out2[2]) {
+    if (!out2) {
+        set_error("ptv_abi_sizes13: out is NULL");
+        return PTV_E_ARG;
+    }
+    out2[0] = (int64_t)sizeof(ptv_mg_params);
+    out2[1] = (int64_t)sizeof(ptv_mg_stats);
+    return PTV_OK;
+}
+
 const char *ptv_last_error(void) { return g_last_error.c_str(); }
 
 int ptv_device_count(int *out) {

@@ -106,6 +106,7 @@ struct ptv_ctx {
     ptv::VarWork var;                                                 // variational cleaning: CG vectors, state
     ptv::PressWork press;                                             // pressure recovery: stencil scratch, CG vectors
     ptv::Event ev_press[4];                                           // chain start, around the divergence, end
+    ptv::MgWork mg;                                                   // multigrid preconditioner: operators, coarse vectors
     ptv::DevBuf<double> flow_part, flow_res;                          // flow analysis: per-block partials, reduced rows
     ptv::Event ev_flow0, ev_flow1;                                    // around its kernels
     ptv::DevBuf<double> drag_part, drag_res;                          // interface drag / gradient sums: partials, rows

@@ -220,6 +220,20 @@ int press_solve(ptv_ctx *c, const ptv_pressure_params *prm, const GridSpec &g, c
     return PTV_OK;
 }
 
+// ---- the preconditioned anchored solve (ptv_multigrid.hip, press_pcg) ----
+// the family's checks, then the multigrid parameters and the level table (host arithmetic only)
+int mg_check(ptv_ctx *c, const ptv_pressure_params *prm, const ptv_mg_params *mg, GridSpec &g, MgPlan &plan) {
+    PTV_TRY(press_check(c, prm, g));
+    return mg_plan(g, mg, plan);
+}
+
+int needs_dirichlet(bool given, const char *who) {
+    if (given) return PTV_OK;
+    set_error(std::string(who) + ": the multigrid preconditioner serves the anchored (CG) solve only; "
+              "the solve without a Dirichlet set is LSQR and takes no preconditioner");
+    return PTV_E_UNSUPPORTED;
+}
+
 // the parameters of a host call with its staged fluid mask in place of the caller's
 ptv_pressure_params on_device(const ptv_pressure_params *prm, const uint8_t *M) {
     ptv_pressure_params dp = *prm;
@@ -540,6 +554,163 @@ int ptv_pressure_recover(ptv_ctx *c, const ptv_pressure_params *prm, const doubl
     double *p = sg.room<double>(3, bytes);
     PTV_TRY(sg.rc);
     PTV_TRY(ptv_pressure_recover_dev(c, &dp, d[0], d[1], d[2], p, sg.s, st));
+    sg.back(P, 3, bytes);
+    return sg.sync();
+}
+
+int ptv_poisson_mg_apply_dev(ptv_ctx *c, const ptv_pressure_params *prm, const ptv_mg_params *mg,
+                             const uint8_t *dirichlet, const double *r, double *z, void *stream,
+                             ptv_mg_stats *mst) {
+    GridSpec g{};
+    MgPlan plan;
+    PTV_TRY(mg_check(c, prm, mg, g, plan));
+    PTV_TRY(ptrs_check(c, r && z && r != z, "poisson_mg_apply: NULL input or output, or z aliases r"));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    PTV_TRY(mg_setup(c->mg, plan, prm->fluid_mask, dirichlet, s));
+    PTV_TRY(c->mg.ev[2].record(s));
+    PTV_TRY(mg_vcycle(c->mg, plan, prm->fluid_mask, dirichlet, nullptr, r, z, nullptr, s));
+    PTV_TRY(c->mg.ev[3].record(s));
+    PTV_HIP(hipStreamSynchronize(s));
+    if (mst) {
+        PTV_TRY(mg_fill_stats(c->mg, plan, mst));
+        float ms = 0.f;
+        PTV_HIP(hipEventElapsedTime(&ms, c->mg.ev[2], c->mg.ev[3]));
+        mst->ms_vcycle_median = ms;
+    }
+    return PTV_OK;
+}
+
+int ptv_poisson_mg_apply(ptv_ctx *c, const ptv_pressure_params *prm, const ptv_mg_params *mg,
+                         const uint8_t *dirichlet, const double *r, double *z, ptv_mg_stats *mst) {
+    GridSpec g{};
+    MgPlan plan;
+    PTV_TRY(mg_check(c, prm, mg, g, plan));
+    PTV_TRY(ptrs_check(c, r && z, "poisson_mg_apply: NULL input or output"));
+    Stage sg(c);
+    const size_t n = voxels(prm), bytes = n * sizeof(double);
+    const double *dr = sg.in<double>(0, r, bytes);
+    double *dz = sg.room<double>(1, bytes);
+    const ptv_pressure_params dp = on_device(prm, sg.mask(prm->fluid_mask, n));
+    const uint8_t *dir = dirichlet ? sg.in<uint8_t>(4, dirichlet, n) : nullptr;
+    PTV_TRY(sg.rc);
+    PTV_TRY(ptv_poisson_mg_apply_dev(c, &dp, mg, dir, dr, dz, sg.s, mst));
+    sg.back(z, 1, bytes);
+    return sg.sync();
+}
+
+int ptv_poisson_solve_mg_dev(ptv_ctx *c, const ptv_pressure_params *prm, const double *rhs, const double *Fx,
+                             const double *Fy, const double *Fz, const uint8_t *dirichlet, double *X, void *stream,
+                             const ptv_mg_params *mg, ptv_pressure_stats *st, ptv_mg_stats *mst) {
+    GridSpec g{};
+    MgPlan plan;
+    PTV_TRY(poisson_solve_args(c, prm, rhs, Fx, Fy, Fz, X, g));
+    PTV_TRY(mg_plan(g, mg, plan));
+    PTV_TRY(needs_dirichlet(dirichlet != nullptr, "poisson_solve_mg"));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    ptv_pressure_stats out{};
+    out.anchor_plane = -1;
+    PTV_TRY(c->ev_press[0].record(s));
+    if (!rhs) {
+        PTV_TRY(c->press.rhs.ensure(voxels(prm)));
+        PTV_TRY(press_divergence(g, prm->wall_bc == PTV_WALL_INHOMOGENEOUS, prm->fluid_mask, Fx, Fy, Fz,
+                                 c->press.rhs.p, s));
+        rhs = c->press.rhs.p;
+    }
+    PTV_TRY(press_pcg(c->press, c->mg, plan, g, prm->rtol, prm->maxiter, prm->fluid_mask, dirichlet, rhs, X, s, &out,
+                      mst));
+    PTV_TRY(c->ev_press[3].record(s));
+    PTV_HIP(hipStreamSynchronize(s));
+    float ms = 0.f;
+    PTV_HIP(hipEventElapsedTime(&ms, c->ev_press[0], c->ev_press[3]));
+    out.ms_total = ms;
+    if (st) *st = out;
+    return PTV_OK;
+}
+
+int ptv_poisson_solve_mg(ptv_ctx *c, const ptv_pressure_params *prm, const double *rhs, const double *Fx,
+                         const double *Fy, const double *Fz, const uint8_t *dirichlet, double *X,
+                         const ptv_mg_params *mg, ptv_pressure_stats *st, ptv_mg_stats *mst) {
+    GridSpec g{};
+    MgPlan plan;
+    PTV_TRY(poisson_solve_args(c, prm, rhs, Fx, Fy, Fz, X, g));
+    PTV_TRY(mg_plan(g, mg, plan));
+    PTV_TRY(needs_dirichlet(dirichlet != nullptr, "poisson_solve_mg"));
+    Stage sg(c);
+    const size_t n = voxels(prm), bytes = n * sizeof(double);
+    double *F[3] = {nullptr, nullptr, nullptr};
+    double *x = rhs ? sg.in<double>(0, rhs, bytes) : sg.room<double>(0, bytes);
+    if (!rhs) in3(sg, 1, Fx, Fy, Fz, bytes, F);
+    const ptv_pressure_params dp = on_device(prm, sg.mask(prm->fluid_mask, n));
+    const uint8_t *dir = sg.in<uint8_t>(4, dirichlet, n);
+    PTV_TRY(sg.rc);
+    PTV_TRY(ptv_poisson_solve_mg_dev(c, &dp, rhs ? x : nullptr, F[0], F[1], F[2], dir, x, sg.s, mg, st, mst));
+    sg.back(X, 0, bytes);
+    return sg.sync();
+}
+
+int ptv_pressure_recover_mg_dev(ptv_ctx *c, const ptv_pressure_params *prm, const double *U, const double *V,
+                                const double *W, double *P, void *stream, const ptv_mg_params *mg,
+                                ptv_pressure_stats *st, ptv_mg_stats *mst) {
+    GridSpec g{};
+    MgPlan plan;
+    PTV_TRY(pressure_recover_args(c, prm, U, V, W, P, g));
+    PTV_TRY(mg_plan(g, mg, plan));
+    PTV_TRY(needs_dirichlet(prm->anchor != PTV_ANCHOR_NONE, "pressure_recover_mg"));
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    const size_t n = voxels(prm);
+    PTV_TRY(c->press.f.ensure(3 * n));
+    PTV_TRY(c->press.rhs.ensure(n));
+    PTV_TRY(c->press.dir.ensure(n));
+    double *F = c->press.f.p;
+    const uint8_t *M = prm->fluid_mask;
+    ptv_pressure_stats out{};
+    out.anchor_plane = -1;
+    if (mst) *mst = ptv_mg_stats{};
+    PTV_TRY(c->ev_press[0].record(s));
+    PTV_TRY(press_force(c->press, g, prm->mu, prm->rho, M, U, V, W, F, F + n, F + 2 * n, s, &out));
+    if (out.n_fluid == 0) {  // physics.py:274-276
+        PTV_HIP(hipMemsetAsync(P, 0, n * sizeof(double), s));
+        PTV_HIP(hipStreamSynchronize(s));
+        if (st) *st = out;
+        return PTV_OK;
+    }
+    PTV_TRY(c->ev_press[1].record(s));
+    PTV_TRY(press_divergence(g, prm->wall_bc == PTV_WALL_INHOMOGENEOUS, M, F, F + n, F + 2 * n, c->press.rhs.p, s));
+    PTV_TRY(c->ev_press[2].record(s));
+    // velocity_analysis.py:304-321: np.mean(w[mask]) >= 0 has the sign of the sum
+    const bool positive = prm->flow_direction == 1 || (prm->flow_direction == 0 && out.sum_w >= 0.0);
+    const bool last = (prm->anchor == PTV_ANCHOR_OUTLET) == positive;
+    out.anchor_plane = last ? g.nz - 1 : 0;
+    PTV_TRY(press_anchor_plane(g, out.anchor_plane, M, c->press.dir.p, s));
+    PTV_TRY(press_pcg(c->press, c->mg, plan, g, prm->rtol, prm->maxiter, M, c->press.dir.p, c->press.rhs.p, P, s, &out,
+                      mst));
+    PTV_TRY(c->ev_press[3].record(s));
+    PTV_HIP(hipStreamSynchronize(s));
+    float ms = 0.f;
+    PTV_HIP(hipEventElapsedTime(&ms, c->ev_press[1], c->ev_press[2]));
+    out.ms_divergence = ms;
+    PTV_HIP(hipEventElapsedTime(&ms, c->ev_press[0], c->ev_press[3]));
+    out.ms_total = ms;
+    if (st) *st = out;
+    return PTV_OK;
+}
+
+int ptv_pressure_recover_mg(ptv_ctx *c, const ptv_pressure_params *prm, const double *U, const double *V,
+                            const double *W, double *P, const ptv_mg_params *mg, ptv_pressure_stats *st,
+                            ptv_mg_stats *mst) {
+    GridSpec g{};
+    MgPlan plan;
+    PTV_TRY(pressure_recover_args(c, prm, U, V, W, P, g));
+    PTV_TRY(mg_plan(g, mg, plan));
+    PTV_TRY(needs_dirichlet(prm->anchor != PTV_ANCHOR_NONE, "pressure_recover_mg"));
+    Stage sg(c);
+    const size_t bytes = voxels(prm) * sizeof(double);
+    double *d[3];
+    in3(sg, 0, U, V, W, bytes, d);
+    const ptv_pressure_params dp = on_device(prm, sg.mask(prm->fluid_mask, voxels(prm)));
+    double *p = sg.room<double>(3, bytes);
+    PTV_TRY(sg.rc);
+    PTV_TRY(ptv_pressure_recover_mg_dev(c, &dp, d[0], d[1], d[2], p, sg.s, mg, st, mst));
     sg.back(P, 3, bytes);
     return sg.sync();
 }

@@ -88,6 +88,38 @@ __device__ __forceinline__ void cg_step(int phase, const CgCfg &cfg, double *__r
     }
 }
 
+// ---- the same recurrence with a preconditioner (scipy's cg with M=) ----
+// The top of an iteration splits in two around z = M r: PH_PTOP0 / PH_PTOP hold the convergence test
+// on r^2 (as PH_TOP0 / PH_TOP), PH_PRHO takes rho = r z and beta.  PH_INIT, PH_ALPHA and PH_END are
+// cg_step's.  A solver names the slot of its state that keeps r z as last summed.
+enum { PH_PTOP0 = 64, PH_PTOP, PH_PRHO };
+
+__device__ __forceinline__ bool pcg_in_iteration(int phase) {
+    return in_iteration(phase) || phase == PH_PTOP0 || phase == PH_PTOP || phase == PH_PRHO;
+}
+
+// r0: r^2 for PH_PTOP, r z for PH_PRHO (PH_PTOP0 reads no sum); the other phases as in cg_step
+__device__ __forceinline__ void pcg_step(int phase, const CgCfg &cfg, double *__restrict__ st, int rz_slot,
+                                         double r0) {
+    switch (phase) {
+    case PH_PTOP0:
+    case PH_PTOP: {
+        const double rr = phase == PH_PTOP0 ? st[S_RR] : r0;
+        st[S_RR] = rr;
+        if (sqrt(rr) < st[S_THR]) st[S_STOP] = 1.0;  // info = 0
+        break;
+    }
+    case PH_PRHO:
+        st[rz_slot] = r0;
+        st[S_RHO] = r0;
+        st[S_BETA] = st[S_ITN] == 0.0 ? 0.0 : r0 / st[S_RHO_PREV];
+        break;
+    default:
+        cg_step(phase, cfg, st, r0);
+        break;
+    }
+}
+
 }  // namespace cg
 
 // ---- host ----

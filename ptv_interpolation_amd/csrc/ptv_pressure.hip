@@ -50,7 +50,7 @@ namespace {
 using namespace cg;
 
 // device-resident state (doubles): the CG recurrence, the solve's counts, then what the force pass leaves
-enum { S_NDIR = S_CG_COUNT, S_NFLUID, S_COUNT, F_BULK = 16, F_SFX, F_SFY, F_SFZ, F_SW, F_NFLUID, F_COUNT };
+enum { S_NDIR = S_CG_COUNT, S_NFLUID, S_RZ, S_COUNT, F_BULK = 16, F_SFX, F_SFY, F_SFZ, F_SW, F_NFLUID, F_COUNT };
 constexpr int kStateLen = 24;
 static_assert(S_COUNT <= F_BULK && F_COUNT <= kStateLen, "state length");
 
@@ -395,6 +395,68 @@ __global__ __launch_bounds__(kGridThreads) void k_pq(PArgs a, const double *__re
     if (threadIdx.x == 0) part[blockIdx.x] = ss;
 }
 
+// k_pq for the preconditioned solve: p' = z + beta p on active voxels (into Pn), q = A p', partial sums
+// of p' q, with q in the form of the assembled matrix the oracle multiplies by, so that the product
+// is scipy's bits: the diagonal d = 0 + h^-2 of every fluid neighbour inside the domain in the order
+// x-, x+, y-, y+, z-, z+ (Dirichlet ones included: their columns are eliminated, their count stays),
+// and the row sum in ascending column order, q = 0 + w p'(z-) + w p'(y-) + w p'(x-) + (-d) p' + w p'(x+)
+// + w p'(y+) + w p'(z+).  A Dirichlet neighbour's p' is 0 and adds nothing.  The plain solve keeps
+// k_pq's difference form, which its own oracle (the slice operator) has.
+template <int VEC>
+__global__ __launch_bounds__(kGridThreads) void k_pqm(PArgs a, const double *__restrict__ st,
+                                                      const double *__restrict__ Z, const double *__restrict__ P,
+                                                      double *__restrict__ Pn, double *__restrict__ Q,
+                                                      const uint8_t *__restrict__ M, const uint8_t *__restrict__ Dir,
+                                                      double *__restrict__ part) {
+    if (st[S_STOP] != 0.0) return;
+    const double beta = st[S_BETA];
+    double ss = 0.0;
+#pragma unroll
+    for (int it = 0; it < kGridItems; ++it) {
+        Pos p;
+        if (!group_pos<VEC>(a, it, p)) break;
+        const MV<VEC> act = active_of<VEC>(M, Dir, p.i);
+        const DV<VEC> zc = ldd<VEC>(Z + p.i), pc = ldd<VEC>(P + p.i);
+        DV<VEC> c, q;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+            const unsigned i = p.i + e;
+            const int x = p.x + e;
+            c.e[e] = 0.0;
+            q.e[e] = 0.0;
+            if (!act.e[e]) continue;
+            const double xi = zc.e[e] + beta * pc.e[e];
+            const Clamp n = clamped(a, i, x, p.y, p.z);
+            // a clamped index is the voxel itself: the face is then outside the domain
+            const bool fxm = n.xm != i && M[n.xm], fxp = n.xp != i && M[n.xp], fym = n.ym != i && M[n.ym],
+                       fyp = n.yp != i && M[n.yp], fzm = n.zm != i && M[n.zm], fzp = n.zp != i && M[n.zp];
+            double d = 0.0;
+            if (fxm) d += a.ih2[0];
+            if (fxp) d += a.ih2[0];
+            if (fym) d += a.ih2[1];
+            if (fyp) d += a.ih2[1];
+            if (fzm) d += a.ih2[2];
+            if (fzp) d += a.ih2[2];
+            // an inactive voxel's z and p are 0, so the owners' expression gives the neighbours 0 too
+            double acc = 0.0;
+            if (fzm) acc += a.ih2[2] * (Z[n.zm] + beta * P[n.zm]);
+            if (fym) acc += a.ih2[1] * (Z[n.ym] + beta * P[n.ym]);
+            if (fxm) acc += a.ih2[0] * (Z[n.xm] + beta * P[n.xm]);
+            acc += (-d) * xi;
+            if (fxp) acc += a.ih2[0] * (Z[n.xp] + beta * P[n.xp]);
+            if (fyp) acc += a.ih2[1] * (Z[n.yp] + beta * P[n.yp]);
+            if (fzp) acc += a.ih2[2] * (Z[n.zp] + beta * P[n.zp]);
+            c.e[e] = xi;
+            q.e[e] = acc;
+            ss += xi * acc;
+        }
+        std_<VEC>(Pn + p.i, c);
+        std_<VEC>(Q + p.i, q);
+    }
+    ss = block_sum(ss);
+    if (threadIdx.x == 0) part[blockIdx.x] = ss;
+}
+
 // x += alpha p;  r -= alpha q;  partial sums of the new r^2
 template <int VEC>
 __global__ __launch_bounds__(kGridThreads) void k_pxr(PArgs a, const double *__restrict__ st,
@@ -476,6 +538,34 @@ __global__ __launch_bounds__(kGridFinalThreads) void k_pcg_scalar(int phase, CgC
             st[S_NFLUID] = r[2];
         }
     }
+}
+
+// partial sums of r z (the preconditioned solve's rho); both are 0 at every voxel that is not active
+template <int VEC>
+__global__ __launch_bounds__(kGridThreads) void k_rz(PArgs a, const double *__restrict__ st,
+                                                     const double *__restrict__ R, const double *__restrict__ Z,
+                                                     double *__restrict__ part) {
+    if (st[S_STOP] != 0.0) return;
+    double ss = 0.0;
+#pragma unroll
+    for (int it = 0; it < kGridItems; ++it) {
+        Pos p;
+        if (!group_pos<VEC>(a, it, p)) break;
+        const DV<VEC> r = ldd<VEC>(R + p.i), z = ldd<VEC>(Z + p.i);
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) ss += r.e[e] * z.e[e];
+    }
+    ss = block_sum(ss);
+    if (threadIdx.x == 0) part[blockIdx.x] = ss;
+}
+
+// the second stage and the scalar step of the preconditioned recurrence's own phases
+__global__ __launch_bounds__(kGridFinalThreads) void k_ppcg_scalar(int phase, CgCfg cfg, double *__restrict__ st,
+                                                                    const double *__restrict__ part, unsigned npart) {
+    if (pcg_in_iteration(phase) && st[S_STOP] != 0.0) return;
+    const double r0 = phase == PH_PTOP0 ? 0.0 : partial_sum(part, npart);
+    if (threadIdx.x != 0) return;
+    pcg_step(phase, cfg, st, S_RZ, r0);
 }
 
 int make_args(const GridSpec &g, PArgs &a) {
@@ -633,6 +723,103 @@ int press_cg(PressWork &wk, const GridSpec &g, double rtol, int maxiter, const u
         PTV_HIP(hipEventElapsedTime(&ms, wk.ev[2], wk.ev[4 + batches]));
         st->ms_solve = ms;
         PTV_TRY(median_iter_ms(wk.ev, 3, batch_iters, st->itn, st->ms_solve, st->ms_iter_median));
+    }
+    return PTV_OK;
+}
+
+// One iteration (scipy _isolve/iterative.py, cg with M):
+//     k_ppcg_scalar PTOP:  rr = sum r^2;  ||r|| < rtol ||b|| stops, info 0
+//     mg_vcycle:           z = M r  (q is its level-0 scratch: nothing reads q before k_pqm rewrites it)
+//     k_rz, PRHO:          rho = sum r z, beta = rho / rho_prev
+//     k_pqm:               p' = z + beta p,  q = A p' in the assembled matrix's form,  partial sums of p' q
+//     k_pcg_scalar ALPHA, k_pxr: as in press_cg
+// The first V-cycle of every polling batch is timed (events 4 + 2 b, 5 + 2 b of the multigrid work).
+int press_pcg(PressWork &wk, MgWork &mg, const MgPlan &plan, const GridSpec &g, double rtol, int maxiter,
+              const uint8_t *M, const uint8_t *Dir, const double *B, double *X, hipStream_t s,
+              ptv_pressure_stats *st, ptv_mg_stats *mst) {
+    PArgs a{};
+    PTV_TRY(make_args(g, a));
+    if (!std::isfinite(rtol) || maxiter < 0) {
+        set_error("pressure: rtol must be finite and maxiter non-negative");
+        return PTV_E_ARG;
+    }
+    if (!Dir) {
+        set_error("pressure: the preconditioned solve needs a Dirichlet grid");
+        return PTV_E_UNSUPPORTED;
+    }
+    const size_t n = a.n, nbytes = n * sizeof(double);
+    const bool vec2 = a.nx % 2 == 0 && all_aligned16(B, X) && aligned(M, 2) && aligned(Dir, 2);
+    const unsigned nb = blocks_for(a.n, vec2 ? 2 : 1);
+    for (DevBuf<double> *b : {&wk.x, &wk.r, &wk.p[0], &wk.p[1], &wk.q, &wk.z}) PTV_TRY(b->ensure(n));
+    PTV_TRY(wk.part.ensure(5 * (size_t)blocks_for(a.n, 1)));
+    PTV_TRY(wk.state.ensure(kStateLen));
+    PTV_TRY(wk.h_state.ensure(3 * kStateLen));
+    double *h_final = wk.h_state.p + 2 * kStateLen;
+    const size_t sbytes = kStateLen * sizeof(double);
+    const CgCfg cfg{rtol, maxiter};
+    const double *cst = wk.state.p;
+    auto pscalar = [&](int phase) -> int {
+        hipLaunchKernelGGL(k_ppcg_scalar, dim3(1), dim3(kGridFinalThreads), 0, s, phase, cfg, wk.state.p, wk.part.p, nb);
+        PTV_HIP(hipGetLastError());
+        return PTV_OK;
+    };
+
+    PTV_TRY(record_event(wk.ev, 2, s));
+    PTV_TRY(mg_setup(mg, plan, M, Dir, s));
+    PTV_HIP(hipMemsetAsync(wk.p[0].p, 0, nbytes, s));
+    PTV_HIP(hipMemsetAsync(wk.p[1].p, 0, nbytes, s));
+    PTV_HIP(hipMemsetAsync(wk.q.p, 0, nbytes, s));
+    GRID_LAUNCH(k_pinit, vec2, nb, s, a, B, M, Dir, wk.x.p, wk.r.p, wk.part.p, nb);
+    PTV_TRY(scalar(wk, PH_INIT, cfg, nb, s));
+    PTV_TRY(record_event(wk.ev, 3, s));
+    int cur = 0;  // p[cur] holds the last direction
+    std::vector<int> batch_iters;
+    PTV_TRY(poll_batches(s, wk.state.p, wk.h_state.p, kStateLen, wk.ev, maxiter, [&](int it) -> int {
+        PTV_TRY(pscalar(it == 0 ? PH_PTOP0 : PH_PTOP));
+        const bool timed = it % kPoll == 0;
+        if (timed) PTV_TRY(record_event(mg.ev, 4 + 2 * (size_t)(it / kPoll), s));
+        PTV_TRY(mg_vcycle(mg, plan, M, Dir, cst, wk.r.p, wk.z.p, wk.q.p, s));
+        if (timed) PTV_TRY(record_event(mg.ev, 5 + 2 * (size_t)(it / kPoll), s));
+        GRID_LAUNCH(k_rz, vec2, nb, s, a, cst, (const double *)wk.r.p, (const double *)wk.z.p, wk.part.p);
+        PTV_TRY(pscalar(PH_PRHO));
+        GRID_LAUNCH(k_pqm, vec2, nb, s, a, cst, (const double *)wk.z.p, (const double *)wk.p[cur].p, wk.p[cur ^ 1].p,
+                    wk.q.p, M, Dir, wk.part.p);
+        cur ^= 1;
+        PTV_TRY(scalar(wk, PH_ALPHA, cfg, nb, s));
+        GRID_LAUNCH(k_pxr, vec2, nb, s, a, cst, (const double *)wk.p[cur].p, (const double *)wk.q.p, wk.x.p, wk.r.p, M,
+                    Dir, wk.part.p);
+        return PTV_OK;
+    }, batch_iters));
+    const size_t batches = batch_iters.size();
+    PTV_TRY(scalar(wk, PH_END, cfg, nb, s));
+    PTV_TRY(record_event(wk.ev, 4 + batches, s));
+    GRID_LAUNCH(k_pout, vec2, nb, s, a, cst, (const double *)wk.x.p, M, Dir, X);
+    PTV_HIP(hipMemcpyAsync(h_final, wk.state.p, sbytes, hipMemcpyDeviceToHost, s));
+    PTV_HIP(hipStreamSynchronize(s));
+    const int itn = (int)h_final[S_ITN];
+    if (st) {
+        st->solver = 0;
+        st->itn = itn;
+        st->info = (int32_t)h_final[S_INFO];
+        st->bnorm = h_final[S_BNORM];
+        st->rnorm = sqrt(h_final[S_RR]);
+        st->n_fluid = (int64_t)h_final[S_NFLUID];
+        st->n_dirichlet = (int64_t)h_final[S_NDIR];
+        float ms = 0.f;
+        PTV_HIP(hipEventElapsedTime(&ms, wk.ev[2], wk.ev[4 + batches]));
+        st->ms_solve = ms;
+        PTV_TRY(median_iter_ms(wk.ev, 3, batch_iters, st->itn, st->ms_solve, st->ms_iter_median));
+    }
+    if (mst) {
+        PTV_TRY(mg_fill_stats(mg, plan, mst));
+        std::vector<double> per;  // the timed V-cycles that ran: those of the batches begun before the stop
+        for (size_t b = 0; b < batches && (int)(b * kPoll) < itn; ++b) {
+            float ms = 0.f;
+            PTV_HIP(hipEventElapsedTime(&ms, mg.ev[4 + 2 * b], mg.ev[5 + 2 * b]));
+            per.push_back(ms);
+        }
+        std::sort(per.begin(), per.end());
+        mst->ms_vcycle_median = per.empty() ? 0.0 : per[per.size() / 2];
     }
     return PTV_OK;
 }

@@ -213,12 +213,26 @@ def compute_force_divergence(fx, fy, fz, mask, dx, dy, dz, wall_bc='zero-neumann
     return _ctx().force_divergence(fx, fy, fz, mask, float(dx), float(dy), float(dz), wall_bc)
 
 
-def solve_poisson(source, mask, dx, dy, dz, force_field=None, wall_bc='inhomogeneous', dirichlet_mask=None, dirichlet_values=None):
+def solve_poisson(source, mask, dx, dy, dz, force_field=None, wall_bc='inhomogeneous', dirichlet_mask=None, dirichlet_values=None,
+                  *, preconditioner=None, multigrid=None):
     """physics.py:264-345 on the GPU: Lap(p) = source (or the divergence of ``force_field``) on the
     fluid voxels.  With a ``dirichlet_mask`` the solve is scipy's ``cg(A, b, tol=1e-10,
     maxiter=3000)``, matrix-free; without one, ``lsqr`` on ``b - mean(b)`` with the reference's
     settings.  Only zero Dirichlet values are supported: for other values the reference subtracts
-    the Dirichlet column from ``b`` and also keeps it in the matrix, which counts it twice."""
+    the Dirichlet column from ``b`` and also keeps it in the matrix, which counts it twice.
+    ``preconditioner='multigrid'`` (opt-in) runs the anchored solve as ``cg(A, b, M=...)`` with the
+    V-cycle of DESIGN.md §25; ``multigrid`` is a dict of its parameters (max_levels, nu,
+    coarse_sweeps, omega), and ``solve_poisson.last_stats['multigrid']`` then holds the hierarchy and
+    its times.  Without a ``dirichlet_mask`` it raises ``NotImplementedError``."""
+    if preconditioner not in (None, 'multigrid'):
+        raise ValueError(f"unknown preconditioner {preconditioner!r} (None or 'multigrid')")
+    if preconditioner is None and multigrid is not None:
+        raise ValueError("multigrid= needs preconditioner='multigrid'")
+    if preconditioner == 'multigrid':
+        _lib.mg_params(multigrid)
+        if dirichlet_mask is None:
+            raise NotImplementedError("preconditioner='multigrid' serves the anchored (CG) solve; without a "
+                                      "dirichlet_mask the solve is LSQR, which takes no preconditioner")
     src = (source,) if force_field is None else tuple(force_field)
     if force_field is None and source is None:
         raise ValueError("either source or force_field is required")
@@ -235,6 +249,10 @@ def solve_poisson(source, mask, dx, dy, dz, force_field=None, wall_bc='inhomogen
     if not mask.any():
         return np.zeros(mask.shape)  # physics.py:275-276
     kw = {"rhs": src[0]} if force_field is None else {"force_field": src}
-    x, st = _ctx().poisson_solve(mask, float(dx), float(dy), float(dz), dirichlet=dm, wall_bc=wall_bc, **kw)
+    if preconditioner == 'multigrid':
+        x, st = _ctx().poisson_solve_mg(mask, float(dx), float(dy), float(dz), dirichlet=dm, wall_bc=wall_bc,
+                                        multigrid=multigrid, **kw)
+    else:
+        x, st = _ctx().poisson_solve(mask, float(dx), float(dy), float(dz), dirichlet=dm, wall_bc=wall_bc, **kw)
     solve_poisson.last_stats = st
     return x

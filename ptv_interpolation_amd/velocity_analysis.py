@@ -389,27 +389,46 @@ def compute_force_field(u, v, w, dx, dy, dz, mu, rho=0, mask=None):
 
 
 def recover_pressure(u, v, w, dx, dy, dz, mu, rho=0, mask=None, wall_bc='zero-neumann', anchor='outlet',
-                     flow_direction='auto', rtol=1e-10, maxiter=3000):
+                     flow_direction='auto', rtol=1e-10, maxiter=3000, *, preconditioner=None, multigrid=None):
     """``compute_pressure_field`` without the report, with the CG settings exposed; returns
     ``(p, stats)``.  ``stats`` carries ``itn``, ``info`` (CG: scipy's; ``anchor='none'``: lsqr's
     istop), ``bnorm``, ``rnorm``, the sums of |fx|, |fy|, |fz| and w over the fluid voxels,
-    ``n_fluid``, ``n_dirichlet``, ``anchor_plane`` and the device times."""
+    ``n_fluid``, ``n_dirichlet``, ``anchor_plane`` and the device times.
+    ``preconditioner='multigrid'`` runs the anchored solve as scipy's ``cg(A, b, M=...)`` with the
+    V-cycle of DESIGN.md §25 (``multigrid``: a dict of max_levels, nu, coarse_sweeps, omega; the
+    stats then carry a ``multigrid`` dict); with ``anchor='none'`` it raises ``NotImplementedError``."""
     fields, mask = _pressure_args(u, v, w, dx, dy, dz, mu, rho, mask)
     _solve_args(wall_bc, anchor)
+    if preconditioner not in (None, 'multigrid'):
+        raise ValueError(f"unknown preconditioner {preconditioner!r} (None or 'multigrid')")
+    if preconditioner is None and multigrid is not None:
+        raise ValueError("multigrid= needs preconditioner='multigrid'")
+    if preconditioner == 'multigrid':
+        _lib.mg_params(multigrid)
+        if anchor == 'none':
+            raise NotImplementedError("preconditioner='multigrid' serves the anchored (CG) solve; anchor='none' "
+                                      "is solved by LSQR, which takes no preconditioner")
     if not np.isfinite(rtol) or int(maxiter) != maxiter or maxiter < 0:
         raise ValueError(f"rtol must be finite and maxiter an integer >= 0, got {rtol!r}, {maxiter!r}")
     if flow_direction not in ("positive", "negative"):
         flow_direction = "auto"  # the reference's else branch (:310)
     if mask.size == 0:
         return np.zeros(mask.shape), {"n_fluid": 0}
+    if preconditioner == 'multigrid':
+        return _ctx().pressure_recover_mg(*fields, mask, float(dx), float(dy), float(dz), float(mu), float(rho),
+                                          wall_bc, anchor, flow_direction, multigrid=multigrid, rtol=float(rtol),
+                                          maxiter=int(maxiter))
     return _ctx().pressure_recover(*fields, mask, float(dx), float(dy), float(dz), float(mu), float(rho), wall_bc,
                                    anchor, flow_direction, rtol=float(rtol), maxiter=int(maxiter))
 
 
-def compute_pressure_field(u, v, w, dx, dy, dz, mu, rho=0, mask=None, wall_bc='zero-neumann', anchor='outlet', flow_direction='auto'):
+def compute_pressure_field(u, v, w, dx, dy, dz, mu, rho=0, mask=None, wall_bc='zero-neumann', anchor='outlet', flow_direction='auto',
+                           *, preconditioner=None, multigrid=None):
     """velocity_analysis.py:190-330 on the GPU: the relative pressure from the pressure Poisson
-    equation; prints the reference's report.  ``mask=None`` means all fluid; the result is float64."""
-    p, st = recover_pressure(u, v, w, dx, dy, dz, mu, rho, mask, wall_bc, anchor, flow_direction)
+    equation; prints the reference's report.  ``mask=None`` means all fluid; the result is float64.
+    ``preconditioner`` and ``multigrid`` as in ``recover_pressure``."""
+    p, st = recover_pressure(u, v, w, dx, dy, dz, mu, rho, mask, wall_bc, anchor, flow_direction,
+                             preconditioner=preconditioner, multigrid=multigrid)
     print(f"Computing pressure field source term (mu={mu}, rho={rho}, wall_bc={wall_bc}, flow={flow_direction})...")
     n = np.float64(st["n_fluid"])
     with np.errstate(invalid="ignore"):  # a mask without fluid: the reference's means of nothing are NaN

@@ -22,7 +22,9 @@ The GPU drag agrees with the reference to the rounding of a reordered sum and ad
 With ``PTV_GPU_PRESSURE=1``, independently, ``compute_pressure_field`` (:190-330) is replaced in the
 same way.  The GPU pressure agrees with the reference normwise (its force field and right-hand side
 bit for bit); it does not need the ``tol=`` keyword that scipy 1.14 removed from
-``cg``, which the reference's ``solve_poisson`` still passes.
+``cg``, which the reference's ``solve_poisson`` still passes.  ``PTV_GPU_PRESSURE_PRECOND=multigrid``
+on top of it runs the anchored solve with the multigrid preconditioner; for
+``anchor='none'`` it is ignored, with one printed line saying so.
 
 With ``PTV_GPU_DRAG_MESH=1``, independently, ``compute_interface_drag_mesh`` (:513-657) is replaced in
 the same way: marching cubes stays on the host (scikit-image is required, there is no staircase
@@ -133,5 +135,19 @@ if _ref is None:
     for _n in _PRESSURE_NAMES:
         globals()[_n] = getattr(_gpu, _n)
 elif _os.environ.get("PTV_GPU_PRESSURE") == "1":
-    compute_pressure_field = _gpu.compute_pressure_field
-    _ref.compute_pressure_field = _gpu.compute_pressure_field
+    if _os.environ.get("PTV_GPU_PRESSURE_PRECOND") == "multigrid":
+        def compute_pressure_field(u, v, w, dx, dy, dz, mu, rho=0, mask=None, wall_bc='zero-neumann', anchor='outlet',
+                                   flow_direction='auto'):
+            """The GPU ``compute_pressure_field`` with the multigrid-preconditioned anchored solve;
+            ``anchor='none'`` (LSQR) takes no preconditioner and runs as without the switch."""
+            pre = 'multigrid'
+            if anchor == 'none':
+                print("PTV_GPU_PRESSURE_PRECOND=multigrid ignored: anchor='none' is solved by LSQR")
+                pre = None
+            p = _gpu.compute_pressure_field(u, v, w, dx, dy, dz, mu, rho, mask, wall_bc, anchor, flow_direction,
+                                            preconditioner=pre)
+            compute_pressure_field.last_stats = _gpu.compute_pressure_field.last_stats
+            return p
+    else:
+        compute_pressure_field = _gpu.compute_pressure_field
+    _ref.compute_pressure_field = compute_pressure_field
