@@ -621,6 +621,17 @@ __device__ __forceinline__ double vmax_f64(double a, double b) {
     return r;
 }
 
+// Prefilter bit masks: m = 2 m + (s <= t), the compare into the carry register and one
+// add-with-carry of m to itself (shift and insert in one vector instruction).  An unordered
+// compare is false, as `s <= t` is.
+__device__ __forceinline__ void shift_in_le(uint32_t &m, float s, float t) {
+    asm("v_cmp_le_f32 vcc, %[s], %[t]\n\t"
+        "v_addc_co_u32 %[m], vcc, %[m], %[m], vcc"
+        : [m] "+v"(m)
+        : [s] "v"(s), [t] "v"(t)
+        : "vcc");
+}
+
 template <int KMAX>
 __device__ __forceinline__ void insert(double (&bd)[KMAX], int (&bp)[KMAX], double d2, int p) {
     // Ascending carry sweep: m_j = d2 < bd[j] is monotone in j over the sorted list; from the
@@ -875,6 +886,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(knn_waves<K
     // so give XCD x a contiguous range of tiles (neighbouring tiles share cell rows and
     // particle records; each XCD has its own L2)
     constexpr bool KEYS = kKeyList<KMAX, EXACT>;
+    // the trimmed prefilter mask, copy-window test and row setup (below) are compiled for the pair
+    // lists of the search proper only (k <= 12): in some key-list and exact-repair instantiations
+    // they cost scratch (the gfx950 resource table)
+    constexpr bool kTrimPair = !KEYS && !EXACT;
     const int lb = (int)(blockIdx.y * gridDim.x + blockIdx.x);  // linear dispatch order
     if (lb >= a.nblocks) return;                                  // 2-D grid padding (block-uniform)
     if (a.gate != nullptr && !(__longlong_as_double((long long)*a.gate) <= a.gate_halo))
@@ -1546,7 +1561,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(knn_waves<K
                 const int ng = min(64, nbuf - g0);
                 // candidate g0 + j ends at bit nb - 1 - j (shift-in order keeps the loop rolled)
                 const int nb = (ng + 3) & ~3;
-                auto mask4 = [&](int i0) -> uint32_t {
+                auto d2x4 = [&](int i0, f32x2 &s0, f32x2 &s1) {
                     // 4 candidates as two packed-fp32 pairs (v_pk_add / v_pk_mul / v_pk_fma);
                     // slots past nbuf hold stale values, their bits are cleared below
                     const float4 X = *reinterpret_cast<const float4 *>(fbx + g0 + i0);
@@ -1555,26 +1570,53 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(knn_waves<K
                     const f32x2 e0x = qf2x - f32x2{X.x, X.y}, e1x = qf2x - f32x2{X.z, X.w};
                     const f32x2 e0y = qf2y - f32x2{Y.x, Y.y}, e1y = qf2y - f32x2{Y.z, Y.w};
                     const f32x2 e0z = qf2z - f32x2{Z.x, Z.y}, e1z = qf2z - f32x2{Z.z, Z.w};
-                    f32x2 s0 = e0x * e0x, s1 = e1x * e1x;
+                    s0 = e0x * e0x, s1 = e1x * e1x;
                     s0 = __builtin_elementwise_fma(e0y, e0y, s0);
                     s1 = __builtin_elementwise_fma(e1y, e1y, s1);
                     s0 = __builtin_elementwise_fma(e0z, e0z, s0);
                     s1 = __builtin_elementwise_fma(e1z, e1z, s1);
-                    return ((s0.x <= thrf) ? 8u : 0u) | ((s0.y <= thrf) ? 4u : 0u) |
-                           ((s1.x <= thrf) ? 2u : 0u) | ((s1.y <= thrf) ? 1u : 0u);
+                };
+                // pair lists: the four bits shift into a 32-bit word, one compare and one
+                // add-with-carry each (shift_in_le).  The word moves to mh when candidate 32 comes
+                // up (a scalar branch), so mh ends with candidates 0-31 and ml with 32-63; the
+                // halves are joined once, mh above ml's nb - 32 bits.  Key lists keep the 64-bit
+                // shift and four selects: the carry form costs some of them scratch.
+                uint32_t mh = 0u, ml = 0u;
+                unsigned long long m64 = 0ull;
+                auto mask4 = [&](int i0) {
+                    f32x2 s0, s1;
+                    d2x4(i0, s0, s1);
+                    if constexpr (kTrimPair) {
+                        if (i0 == 32) {
+                            mh = ml;
+                            ml = 0u;
+                        }
+                        shift_in_le(ml, s0.x, thrf);
+                        shift_in_le(ml, s0.y, thrf);
+                        shift_in_le(ml, s1.x, thrf);
+                        shift_in_le(ml, s1.y, thrf);
+                    } else {
+                        m64 = (m64 << 4) | (((s0.x <= thrf) ? 8u : 0u) | ((s0.y <= thrf) ? 4u : 0u) |
+                                            ((s1.x <= thrf) ? 2u : 0u) | ((s1.y <= thrf) ? 1u : 0u));
+                    }
                 };
                 auto group_mask = [&]() -> unsigned long long {
-                    unsigned long long m = 0ull;
+                    mh = ml = 0u;
+                    m64 = 0ull;
                     if constexpr (MODE == kModeFilter) {
                         // unrolled by 2 for the filter's long candidate streams (search 19.35 ->
                         // 19.14 ms); rolled elsewhere (the headline +0.7 % unrolled)
                         PTV_UNROLL(PTV_MASK_UNROLL_FILTER)
-                        for (int i0 = 0; i0 < ng; i0 += 4) m = (m << 4) | mask4(i0);
+                        for (int i0 = 0; i0 < ng; i0 += 4) mask4(i0);
                     } else {
                         PTV_UNROLL(PTV_MASK_UNROLL)
-                        for (int i0 = 0; i0 < ng; i0 += 4) m = (m << 4) | mask4(i0);
+                        for (int i0 = 0; i0 < ng; i0 += 4) mask4(i0);
                     }
-                    return m & ~((1ull << (nb - ng)) - 1ull);  // stale slots past nbuf
+                    if constexpr (kTrimPair) {
+                        m64 = ml;
+                        if (nb > 32) m64 |= (unsigned long long)mh << (nb - 32);
+                    }
+                    return m64 & ~((1ull << (nb - ng)) - 1ull);  // stale slots past nbuf
                 };
                 unsigned long long m = group_mask();
                 const double4 *gbuf = buf + g0 + nb - 64;  // bit position p <-> gbuf[63 - p]
@@ -1777,14 +1819,26 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(knn_waves<K
                             const int a1 = clampi(floor((bx0 - rx - g.o[0]) * g.ic[0]), g.nc[0]);
                             const int b1 = clampi(floor((bx1 + rx - g.o[0]) * g.ic[0]), g.nc[0]);
                             int lo1 = a1, hi1 = b1, lo2 = 1, hi2 = 0;  // [lo, hi] inclusive runs
-                            if (h2 <= Rpg2 && ccy >= py0 && ccy <= py1 && ccz >= pz0 && ccz <= pz1) {
-                                // row was gathered by the previous pass: only the x extensions are new
-                                const double rxo = sqrt_up(Rpg2 - h2);
-                                const int a0 = clampi(floor((bx0 - rxo - g.o[0]) * g.ic[0]), g.nc[0]);
-                                const int b0 = clampi(floor((bx1 + rxo - g.o[0]) * g.ic[0]), g.nc[0]);
-                                hi1 = a0 - 1;
-                                lo2 = b0 + 1;
-                                hi2 = b1;
+                            // no previous pass, the common case: a scalar branch on the uniform Rp (the
+                            // empty asm keeps the compiler from folding it into the lanes' test and
+                            // computing the old chord under a predicate on every first pass).  Nothing in
+                            // the build guards this: should a later compiler fold it back, the first-pass
+                            // row path of tools/valu_account.py --blocks goes from 295 VALU back to 327
+                            // (profiles/r10_valu/account_new.txt).  Not in the filter's instantiations:
+                            // with the branch the stamped k = 8 filter kernel took 68 B of scratch (the
+                            // gfx950 resource table), without it none.
+                            constexpr bool kRowBranch = kTrimPair && MODE != kModeFilter;
+                            if (!kRowBranch || Rp >= 0.0) {
+                                if constexpr (kRowBranch) asm volatile("");
+                                if (h2 <= Rpg2 && ccy >= py0 && ccy <= py1 && ccz >= pz0 && ccz <= pz1) {
+                                    // row was gathered by the previous pass: only the x extensions are new
+                                    const double rxo = sqrt_up(Rpg2 - h2);
+                                    const int a0 = clampi(floor((bx0 - rxo - g.o[0]) * g.ic[0]), g.nc[0]);
+                                    const int b0 = clampi(floor((bx1 + rxo - g.o[0]) * g.ic[0]), g.nc[0]);
+                                    hi1 = a0 - 1;
+                                    lo2 = b0 + 1;
+                                    hi2 = b1;
+                                }
                             }
                             // both runs' bounds in flight together (an empty run reads cell 0 twice)
 #if PTV_SUBBALL_RUNS
@@ -1889,7 +1943,26 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(knn_waves<K
                     const int i = src + lane;
                     bool keep = false;
                     float ex = 0.f, ey = 0.f, ez = 0.f;
-                    if (i < total) {
+                    if constexpr (kTrimPair) {
+                        // branch-free on every lane (lanes past the end hold record 0 and are masked
+                        // out): the two halves of each axis as one packed-fp32 pair, each sub-ball's
+                        // sum (qx2 + qy2) + qz2 in that order, and the eight compares against the
+                        // wave-uniform radii OR-ed as lane masks on the scalar unit (`|`, not `||`:
+                        // a short circuit puts every compare under its own exec mask)
+                        ex = (float)(p4.x - tcx);
+                        ey = (float)(p4.y - tcy);
+                        ez = (float)(p4.z - tcz);
+                        const f32x2 dx = f32x2{ex, ex} - f32x2{sbx[0], sbx[1]};
+                        const f32x2 dy = f32x2{ey, ey} - f32x2{sby[0], sby[1]};
+                        const f32x2 dz = f32x2{ez, ez} - f32x2{sbz[0], sbz[1]};
+                        const f32x2 qx2 = dx * dx, qy2 = dy * dy, qz2 = dz * dz;
+                        const f32x2 xy0 = qx2 + f32x2{qy2.x, qy2.x}, xy1 = qx2 + f32x2{qy2.y, qy2.y};
+                        const f32x2 s00 = xy0 + f32x2{qz2.x, qz2.x}, s10 = xy1 + f32x2{qz2.x, qz2.x};
+                        const f32x2 s01 = xy0 + f32x2{qz2.y, qz2.y}, s11 = xy1 + f32x2{qz2.y, qz2.y};
+                        keep = (i < total) &
+                               ((s00.x <= sbr2[0]) | (s00.y <= sbr2[1]) | (s10.x <= sbr2[2]) | (s10.y <= sbr2[3]) |
+                                (s01.x <= sbr2[4]) | (s01.y <= sbr2[5]) | (s11.x <= sbr2[6]) | (s11.y <= sbr2[7]));
+                    } else if (i < total) {
                         ex = (float)(p4.x - tcx);
                         ey = (float)(p4.y - tcy);
                         ez = (float)(p4.z - tcz);

@@ -1,0 +1,129 @@
+"""Static VALU account of one kernel from its gfx950 assembly, per basic block and per source phase.
+
+    hipcc <the build's flags> --cuda-device-only -S -gline-tables-only csrc/ptv_knn_ka.hip -o ka.s
+    python tools/valu_account.py ka.s 'k_knn_interpILi8ELb0ELi0ELb0' [--blocks]
+
+Every vector-ALU instruction (mnemonic v_*) is charged to the source line of the `.loc` in force.
+Lines of ptv_knn_impl.hpp map to a phase by the anchors below (found by text, so the table follows
+the source as it moves); lines of helper headers (ptv_wave.hpp, the insert networks) are charged to
+the phase of the last ptv_knn_impl.hpp line seen before them in the instruction stream, which is
+the call site in straight-line code.  `--blocks` also lists every basic block with its VALU, SALU,
+LDS and VMEM counts and its most frequent source lines: a loop body is the blocks between a label
+and the backward branch to it, and its count times the stamp build's trip count is the dynamic cost.
+"""
+import collections
+import os
+import re
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+IMPL = os.path.join(ROOT, "ptv_interpolation_amd", "csrc", "ptv_knn_impl.hpp")
+
+# (phase, anchor text of its first line), in source order; a phase runs to the next anchor
+ANCHORS = [
+    ("setup", "void k_knn_interp(KnnKernelArgs a"),
+    ("seeds", "bool seeded = false;"),
+    ("setup2 (radius, sub-boxes)", "double cpass = 0.0;"),
+    ("subballs()", "auto subballs = [&]()"),
+    ("flush: head", "auto flush = [&]()"),
+    ("mask4", "auto d2x4 = [&](int i0"),
+    ("group_mask", "auto group_mask = [&]()"),
+    ("flush: popcount / tighten", "unsigned long long m = group_mask();"),
+    ("merge: key lists", "if constexpr (KEYS && MODE != kModeRadius) {"),
+    ("merge: fill", "int it = 0;"),
+    ("merge: insert body", "for (; it < nit; ++it) {"),
+    ("flush: tail", "if constexpr (KEYS) thr = dmin(thr, kth2());"),
+    ("pass setup", "int py0 = 1, py1 = 0, pz0 = 1, pz1 = 0;"),
+    ("row lambda", "uint32_t rs[2 * kRowsPerLane];"),
+    ("row scan / run table", "int cnt = 0;"),
+    ("window_slot", "auto window_slot = [&](int src)"),
+    ("copy: round head", "uint32_t next_slot = total > 0"),
+    ("copy: window body", "const int i = src + lane;"),
+    ("pass end (exactness)", "// ---- exactness: lanes with k-th distance <= R are final ----"),
+    ("epilogue", "// per-wave stamp record (ptv_debug_stamps)"),
+]
+
+
+def phase_table():
+    lines = open(IMPL).read().splitlines()
+    tab, at = [], 0
+    for name, text in ANCHORS:
+        for i in range(at, len(lines)):
+            if text in lines[i]:
+                tab.append((i + 1, name))
+                at = i + 1
+                break
+        else:
+            raise SystemExit(f"anchor not found after line {at}: {text!r}")
+    return tab
+
+
+def main():
+    path, sym = sys.argv[1], sys.argv[2]
+    show_blocks = "--blocks" in sys.argv
+    tab = phase_table()
+
+    def phase_of(line):
+        name = "before the kernel"
+        for first, n in tab:
+            if line >= first:
+                name = n
+        return name
+
+    files = {}
+    inside = False
+    cur_phase, cur_loc = "setup", ("?", 0)
+    per_phase = collections.Counter()
+    blocks = []  # [label, counters, line counter]
+    blk = None
+    for ln in open(path):
+        s = ln.strip()
+        m = re.match(r"\.file\s+(\d+)\s+(?:\"[^\"]*\"\s+)?\"([^\"]+)\"", s)
+        if m:
+            files[m.group(1)] = os.path.basename(m.group(2))
+        if not inside:
+            if re.match(r"_ZN\S*" + re.escape(sym) + r"\S*:", s):
+                inside = True
+                blk = ["entry", collections.Counter(), collections.Counter()]
+                blocks.append(blk)
+            continue
+        if s.startswith(".Lfunc_end"):
+            break
+        m = re.match(r"(\.LBB\d+_\d+):", s)
+        if m:
+            blk = [m.group(1), collections.Counter(), collections.Counter()]
+            blocks.append(blk)
+            continue
+        m = re.match(r"\.loc\s+(\d+)\s+(\d+)", s)
+        if m:
+            f, line = files.get(m.group(1), m.group(1)), int(m.group(2))
+            cur_loc = (f, line)
+            if f == "ptv_knn_impl.hpp" and line >= tab[0][0]:  # the file's helpers above the kernel: call site
+                cur_phase = phase_of(line)
+            continue
+        m = re.match(r"([a-z][a-z0-9_]+)\b", s)
+        if not m or s.startswith("."):
+            continue
+        op = m.group(1)
+        kind = ("VALU" if op.startswith("v_") else "SALU" if op.startswith("s_") else
+                "LDS" if op.startswith("ds_") else "VMEM" if op.startswith(("global_", "buffer_", "scratch_", "flat_")) else "other")
+        blk[1][kind] += 1
+        if kind == "VALU":
+            per_phase[cur_phase] += 1
+            blk[2][(cur_phase, cur_loc)] += 1
+        if kind == "SALU" and re.search(r"s_c?branch\S*\s+(\.LBB\d+_\d+)", s):
+            blk[1]["->" + re.search(r"(\.LBB\d+_\d+)", s).group(1)] += 1
+    print(f"# {sym}: static VALU instructions per source phase (whole kernel {sum(per_phase.values())})")
+    for _, name in [(0, "before the kernel")] + tab:
+        if per_phase[name]:
+            print(f"{per_phase[name]:6d}  {name}")
+    if show_blocks:
+        print("\n# basic blocks: label, VALU, SALU, LDS, VMEM, branch targets, then phase:file:line x count")
+        for label, c, lc in blocks:
+            tg = " ".join(k for k in c if k.startswith("->"))
+            top = ", ".join(f"{p}:{f}:{l} x{n}" for (p, (f, l)), n in lc.most_common(6))
+            print(f"{label:12s} V{c['VALU']:4d} S{c['SALU']:4d} L{c['LDS']:3d} M{c['VMEM']:3d}  {tg}\n              {top}")
+
+
+if __name__ == "__main__":
+    main()
