@@ -93,6 +93,13 @@ namespace ptv {
 #ifndef PTV_SEED_PEEL
 #define PTV_SEED_PEEL 1
 #endif
+// dev builds: 0 = the earlier form (same-box A/B in profiles/r11_tile_phases/ab.txt)
+#ifndef PTV_TRIM_EPI
+#define PTV_TRIM_EPI 1  // IDW epilogue: one range test, in-range reciprocals, no j < k selects at k == KMAX
+#endif
+#ifndef PTV_WIDE_GUARD
+#define PTV_WIDE_GUARD 1  // eight-slot pair lists: fp32 filters off for tiles whose coordinates leave fp32
+#endif
 #ifndef PTV_SEED_UNROLL_FILTER
 #define PTV_SEED_UNROLL_FILTER 1
 #endif
@@ -555,8 +562,7 @@ __device__ __forceinline__ bool div_by_ok(double amin, double amax, double b) {
 
 // IEEE sqrt for x >= 2^-767: the LLVM gfx9 f64 expansion (rsq seed, two Goldschmidt
 // corrections) without its small-input rescale; tiny, zero and infinite x take sqrt()
-__device__ __forceinline__ double sqrt_cr(double x) {
-    if (!(x >= 0x1p-767 && x < INFINITY)) return sqrt(x);
+__device__ __forceinline__ double sqrt_cr_in(double x) {  // x in [2^-767, inf) only
     const double y = __builtin_amdgcn_rsq(x);
     double g = x * y, h = y * 0.5;
     const double r = fma(-h, g, 0.5);
@@ -564,6 +570,32 @@ __device__ __forceinline__ double sqrt_cr(double x) {
     h = fma(h, r, h);
     g = fma(fma(-g, g, x), h, g);
     return fma(fma(-g, g, x), h, g);
+}
+__device__ __forceinline__ double sqrt_cr(double x) {
+    if (!(x >= 0x1p-767 && x < INFINITY)) return sqrt(x);
+    return sqrt_cr_in(x);
+}
+
+// IEEE 1 / b for b in [2^-750, 2^750] (kRcpLo, kRcpHi): the LLVM gfx9 f64 division expansion for
+// the numerator 1 without its v_div_scale pair, v_div_fmas and v_div_fixup.  In that range the
+// scale steps return their operands and clear vcc (b and 1 / b are normal, the exponents differ by
+// less than 768, the numerator's exponent is above 53), so v_div_fmas is a plain fma and
+// v_div_fixup passes its finite, normal quotient through: the same operations on the same values.
+// q = RN(1 * r) is r itself.  Host emulation of the full and the short sequence with fma
+// (tools/rcp_guard_check.cpp): the scale and fixup steps are identities and the two forms give
+// the same bits on 4.0e8 operands (random over the range's exponents, its edges, the neighbours
+// of every power of two), half of them with the seed anywhere within 2^-22 of 1 / b; with a
+// correctly rounded seed both equal 1.0 / b on all 2.0e8.
+constexpr double kRcpLo = 0x1p-750, kRcpHi = 0x1p750;
+// the IDW epilogue's range for d**p + eps of a full list (see there): its weights and their sum
+// must stay inside rcp_in's range and satisfy div_by_ok
+constexpr double kEpiLo = 0x1p-490, kEpiHi = 0x1p490;
+static_assert(kEpiLo >= kRcpLo && kEpiHi * 16.0 <= kRcpHi, "the weights' sum must stay in rcp_in's range");
+__device__ __forceinline__ double rcp_in(double b) {
+    double r = __builtin_amdgcn_rcp(b);
+    r = fma(fma(-b, r, 1.0), r, r);
+    r = fma(fma(-b, r, 1.0), r, r);
+    return fma(fma(-b, r, 1.0), r, r);
 }
 
 // one voxel's outputs: float64, or float32 (RNE, numpy astype) under PTV_FLAG_OUT_F32
@@ -890,6 +922,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(knn_waves<K
     // lists of the search proper only (k <= 12): in some key-list and exact-repair instantiations
     // they cost scratch (the gfx950 resource table)
     constexpr bool kTrimPair = !KEYS && !EXACT;
+    // the IDW epilogue's in-range forms, same instantiations but eight-slot lists only
+    constexpr bool kTrimEpi = kTrimPair && PTV_TRIM_EPI != 0 && KMAX == 8;
     const int lb = (int)(blockIdx.y * gridDim.x + blockIdx.x);  // linear dispatch order
     if (lb >= a.nblocks) return;                                  // 2-D grid padding (block-uniform)
     if (a.gate != nullptr && !(__longlong_as_double((long long)*a.gate) <= a.gate_halo))
@@ -1048,13 +1082,29 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(knn_waves<K
         const CellGrid &g = a.cg;
         // tile centre: candidates and voxels get fp32 coordinates relative to it
         const double tcx = uniform(0.5 * (bx0 + bx1)), tcy = uniform(0.5 * (by0 + by1)), tcz = uniform(0.5 * (bz0 + bz1));
-        const float qfx = (float)(qx - tcx), qfy = (float)(qy - tcy), qfz = (float)(qz - tcz);
-        const f32x2 qf2x = {qfx, qfx}, qf2y = {qfy, qfy}, qf2z = {qfz, qfz};
         const double bhalf = 0.5 * sqrt_up(((bx1 - bx0) * (bx1 - bx0) + (by1 - by0) * (by1 - by0)) + (bz1 - bz0) * (bz1 - bz0));
+        // The fp32 filters work on coordinates relative to the tile centre.  Up to 2^100 those are
+        // finite floats and an overflowing square is +inf, which every `<=` test accepts.  Beyond
+        // (a.rall bounds every gather radius, so M of a pass stays below this sum) a coordinate
+        // itself becomes +-inf, differences of two become NaN and every test would REJECT: such a
+        // tile (wave-uniform) switches the filters off instead.  Its voxels sit at 0, so a
+        // candidate's fp32 d2 is a sum of squares (finite or +inf, never NaN); its sub-boxes are
+        // points at 0 with infinite radii (Mpass = inf); cpass = inf makes every active lane's
+        // prefilter threshold +inf and keeps the fp32 k-th network from tightening anything; and the
+        // seed bounds, which measure fp32 distances to the voxels, are not formed.  Every candidate
+        // of the gather then reaches the exact f64 test.  Eight-slot pair lists of the search
+        // proper only: in key-list and exact-repair kernels the guard costs 16-80 B of scratch on
+        // the resource table, and the four-slot kernel ran 0.5 % slower with it (k = 4 11.756-11.789
+        // -> 11.805-11.836 ms, profiles/r11_tile_phases/ab.txt), so those keep their range (tested
+        // to 2^80).
+        const bool wide = kTrimPair && KMAX == 8 && PTV_WIDE_GUARD != 0 && !(a.rall + 2.0 * bhalf + 2.0 * fmax(g.cs[0], fmax(g.cs[1], g.cs[2])) < 0x1p100);
+        const float qfx = wide ? 0.f : (float)(qx - tcx), qfy = wide ? 0.f : (float)(qy - tcy),
+                    qfz = wide ? 0.f : (float)(qz - tcz);
+        const f32x2 qf2x = {qfx, qfx}, qf2y = {qfy, qfy}, qf2z = {qfz, qfz};
         bool seeded = false;
 #if PTV_K1_BROADCAST_SEEDS
         if constexpr (KMAX == 1) {
-            if (a.cb.recs != nullptr) {
+            if (a.cb.recs != nullptr && !wide) {
                 // ---- seeds (one-slot list): the 8 corners' nearest particles (lanes 0, 8, ..., 56)
                 //      broadcast to every lane; a lane's smallest distance to them bounds its nearest
                 //      neighbour.  Duplicates are harmless for a minimum: no LDS hash, no barriers ----
@@ -1100,7 +1150,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(knn_waves<K
         } else
 #endif
         if constexpr (KMAX <= 8) {
-            if (a.cb.recs != nullptr) {
+            if (a.cb.recs != nullptr && !wide) {
                 // ---- seeds: the k-NN lists of the tile's 8 coarse-lattice corners.  Every lane's
                 //      k-th smallest distance to their (deduplicated) union bounds its k-th
                 //      neighbour distance from above, usually to within a few ulps, so the gather
@@ -1228,7 +1278,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(knn_waves<K
         // (the launcher gives the key-list interpolation and slot launches no seed records: the
         // union-seed code is not compiled into them, which frees its registers)
         if constexpr (KMAX > 8 && !(KEYS && (MODE == kModeInterp || MODE == kModeSlots))) {
-            if (a.cb.recs != nullptr) {
+            if (a.cb.recs != nullptr && !wide) {
                 // ---- seeds (k > 8): the union of the 8 corners' k-NN lists bounds every voxel's
                 //      k-th distance (measured: within 0.03 % of it in volume, the D(c) + |v - c|
                 //      bound 2.2x).  8 rounds of up to 64 records (one corner per round),
@@ -1478,7 +1528,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(knn_waves<K
 #pragma unroll
             for (int q = 1; q < KMAX; ++q)
                 if (q == a.k - 1) kth = sd[q];
-            if (active && kth < INFINITY) {
+            if (active && kth < INFINITY && !wide) {
                 const double dl = Ms * 1.9073486328125e-06;
                 const double st2 = ((double)kth * (1.0 + 9.5367431640625e-07) + (2.0 * Ms * dl + dl * dl)) * (1.0 + 1e-12);
                 if (st2 < ub2) {
@@ -1532,6 +1582,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(knn_waves<K
                 sbx[h] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cxs), h << 1));
                 sby[h] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cys), h << 3));
                 sbz[h] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(czs), h << 5));
+            }
+            if (wide) {  // point sub-boxes at the voxels' common position
+                sb_hd = 0.f;
+                sbx[0] = sbx[1] = sby[0] = sby[1] = sbz[0] = sbz[1] = 0.f;
             }
         }
         double Mpass = 0.0;  // bound on |coordinate - tile centre| of this pass's candidates
@@ -1772,9 +1826,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(knn_waves<K
                 // tile centre; (s + delta)^2 <= s^2 + 2 M delta + delta^2 bounds the test.
                 const double M = Rg + 2.0 * bhalf + 2.0 * fmax(g.cs[0], fmax(g.cs[1], g.cs[2]));
                 const double delta = M * 4.76837158203125e-07;
-                cpass = 2.0 * M * delta + delta * delta;
+                cpass = wide ? INFINITY : 2.0 * M * delta + delta * delta;
                 thrf = f32_bound(thr, cpass);
-                Mpass = M;
+                Mpass = wide ? INFINITY : M;
                 subballs();
             }
             const double Rpg2 = Rp < 0.0 ? -1.0 : (Rp + g.mg) * (Rp + g.mg);
@@ -1846,7 +1900,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(knn_waves<K
                                 // clip the runs to the union of the 8 sub-balls' chords of this row: a
                                 // particle that can enter any list lies in some sub-ball (the copy filter
                                 // below), so cells outside every chord are never needed.  fp32 on
-                                // tile-relative coordinates, every rounding widened (em).
+                                // tile-relative coordinates, every rounding widened (em).  A `wide` tile
+                                // (Mpass = inf, sub-boxes at 0, radii inf) must come out unclipped: em is
+                                // inf, so ylo / zlo are -inf or NaN (inf - inf) and yhi / zhi +inf or NaN;
+                                // fmaxf returns its other operand for a NaN one, so gy = gz = 0, h2s = 0 <=
+                                // inf, hw = inf, xl = -inf, xh = +inf, and clampi sends s0 to 0 and s1 to
+                                // the last cell.
                                 const float em = (float)(Mpass * 1e-6) + 1e-6f;
                                 const float ylo = (float)(g.o[1] + (double)ccy * g.cs[1] - tcy) - em;
                                 const float yhi = (float)(g.o[1] + (double)(ccy + 1) * g.cs[1] - tcy) + em;
@@ -2275,6 +2334,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(knn_waves<K
         pvw[j] = r.z;
     }
     double w[KMAX];
+    bool epi_done = false;  // kTrimEpi: the wave took the full-list in-range IDW form (wave-uniform)
     if (a.method == PTV_METHOD_SIBSON) {
         // interpolator.py:106-116
         double d[KMAX], t[KMAX];
@@ -2300,38 +2360,88 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(knn_waves<K
         for (int j = 0; j < KMAX; ++j) w[j] = w[j] / s2;
     } else {
         // interpolator.py:143-147
+        if constexpr (kTrimEpi) {
+            // A full list (k == KMAX, wave-uniform) with p = 2 or 1 whose operands are all in range
+            // takes the same IEEE operations in their in-range forms, without the j < k selects:
+            // the list ascends, so bd[0] and bd[KMAX-1] bound every sqrt_cr operand (one test for
+            // the wave instead of one branch pair per neighbour), d**p + eps ascends with it, so
+            // its ends bound every reciprocal's operand in [kEpiLo, kEpiHi] = [2^-490, 2^490]
+            // (inside rcp_in's range).  Every weight is then in [2^-490, 2^490] and s, the sum of
+            // KMAX <= 8 of them, in [2^-490, 2^493]: rcp_in(s) holds, and div_by_ok(wmin, s, s) is
+            // true without forming wmin, since s is within [2^-1000, 2^1000], wmin >= 2^-490 is
+            // above 2^-960 and above s * 2^-1000 <= 2^-507 (the smallest quotient, >= 2^-983, is
+            // normal), and amax = s.  Any lane out of range (d2 = 0 or tiny, an unfilled entry, a
+            // scaled grid, distances spread over more than the range, another power) leaves the
+            // whole wave on the form below.
+            if (k == KMAX && (a.power == 2.0 || a.power == 1.0)) {
+                const bool sq_in = bd[0] >= 0x1p-767 && bd[KMAX - 1] < INFINITY;
+                if (__builtin_amdgcn_ballot_w64(!sq_in) == 0) {
+                    double x[KMAX];
 #pragma unroll
-        for (int j = 0; j < KMAX; ++j) {
-            const double d = sqrt_cr(bd[j]);
-            w[j] = (j < k) ? 1.0 / (np_pow(d, a.power) + a.eps) : 0.0;
+                    for (int j = 0; j < KMAX; ++j) {
+                        const double d = sqrt_cr_in(bd[j]);
+                        x[j] = (a.power == 2.0 ? d * d : d) + a.eps;
+                    }
+                    const bool rc_in = x[0] >= kEpiLo && x[KMAX - 1] <= kEpiHi;
+                    if (__builtin_amdgcn_ballot_w64(!rc_in) == 0) {
+#pragma unroll
+                        for (int j = 0; j < KMAX; ++j) w[j] = rcp_in(x[j]);
+                        const double s = pairwise<KMAX>(w, KMAX);
+                        const double rs = rcp_in(s);
+#pragma unroll
+                        for (int j = 0; j < KMAX; ++j) w[j] = div_by(w[j], s, rs);
+                        epi_done = true;
+                    }
+                }
+            }
         }
-        const double s = pairwise<KMAX>(w, k);
-        // w_j / s through one reciprocal when s and every quotient are normal (w_j > 0 here:
-        // div_by_ok); IEEE division on any lane otherwise
-        double wmin = w[0];
+        if (!epi_done) {
 #pragma unroll
-        for (int j = 1; j < KMAX; ++j)
-            if (j < k) wmin = fmin(wmin, w[j]);
-        const bool fast = div_by_ok(wmin, s, s);
-        if (__builtin_amdgcn_ballot_w64(!fast) == 0) {
-            const double rs = 1.0 / s;
+            for (int j = 0; j < KMAX; ++j) {
+                const double d = sqrt_cr(bd[j]);
+                w[j] = (j < k) ? 1.0 / (np_pow(d, a.power) + a.eps) : 0.0;
+            }
+            const double s = pairwise<KMAX>(w, k);
+            // w_j / s through one reciprocal when s and every quotient are normal (w_j > 0 here:
+            // div_by_ok); IEEE division on any lane otherwise
+            double wmin = w[0];
 #pragma unroll
-            for (int j = 0; j < KMAX; ++j) w[j] = div_by(w[j], s, rs);
-        } else {
+            for (int j = 1; j < KMAX; ++j) {
+                // the weights are quotients, never signalling: no canonicalisation (vmin_f64)
+                if constexpr (kTrimEpi) wmin = (j < k) ? vmin_f64(wmin, w[j]) : wmin;
+                else if (j < k) wmin = fmin(wmin, w[j]);
+            }
+            const bool fast = div_by_ok(wmin, s, s);
+            if (__builtin_amdgcn_ballot_w64(!fast) == 0) {
+                const double rs = 1.0 / s;
 #pragma unroll
-            for (int j = 0; j < KMAX; ++j) w[j] = w[j] / s;
+                for (int j = 0; j < KMAX; ++j) w[j] = div_by(w[j], s, rs);
+            } else {
+#pragma unroll
+                for (int j = 0; j < KMAX; ++j) w[j] = w[j] / s;
+            }
         }
     }
 
     // interpolator.py:150-153: per component, sum_k w * values[idx, c]
     double out[3];
     if constexpr (KMAX <= 8) {
+        if (kTrimEpi && epi_done) {  // a full list: no selects
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            double t[KMAX];
+            for (int c = 0; c < 3; ++c) {
+                double t[KMAX];
 #pragma unroll
-            for (int j = 0; j < KMAX; ++j) t[j] = (j < k) ? w[j] * (c == 0 ? pvu[j] : (c == 1 ? pvv[j] : pvw[j])) : 0.0;
-            out[c] = pairwise<KMAX>(t, k);
+                for (int j = 0; j < KMAX; ++j) t[j] = w[j] * (c == 0 ? pvu[j] : (c == 1 ? pvv[j] : pvw[j]));
+                out[c] = pairwise<KMAX>(t, KMAX);
+            }
+        } else {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                double t[KMAX];
+#pragma unroll
+                for (int j = 0; j < KMAX; ++j) t[j] = (j < k) ? w[j] * (c == 0 ? pvu[j] : (c == 1 ? pvv[j] : pvw[j])) : 0.0;
+                out[c] = pairwise<KMAX>(t, k);
+            }
         }
     } else {
         const double *vb = reinterpret_cast<const double *>(pval);

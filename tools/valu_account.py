@@ -1,7 +1,7 @@
 """Static VALU account of one kernel from its gfx950 assembly, per basic block and per source phase.
 
     hipcc <the build's flags> --cuda-device-only -S -gline-tables-only csrc/ptv_knn_ka.hip -o ka.s
-    python tools/valu_account.py ka.s 'k_knn_interpILi8ELb0ELi0ELb0' [--blocks]
+    python tools/valu_account.py ka.s 'k_knn_interpILi8ELb0ELi0ELb0' [--blocks] [--impl=PATH] [--path=...]
 
 Every vector-ALU instruction (mnemonic v_*) is charged to the source line of the `.loc` in force.
 Lines of ptv_knn_impl.hpp map to a phase by the anchors below (found by text, so the table follows
@@ -18,6 +18,12 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 IMPL = os.path.join(ROOT, "ptv_interpolation_amd", "csrc", "ptv_knn_impl.hpp")
+# the phase anchors are line numbers of the source the assembly was compiled from: for another
+# commit's assembly pass that commit's header, --impl=PATH (the current tree's lines would
+# mis-attribute every phase)
+for _a in sys.argv[3:]:
+    if _a.startswith("--impl="):
+        IMPL = _a[len("--impl="):]
 
 # (phase, anchor text of its first line), in source order; a phase runs to the next anchor
 ANCHORS = [
@@ -117,6 +123,26 @@ def main():
     for _, name in [(0, "before the kernel")] + tab:
         if per_phase[name]:
             print(f"{per_phase[name]:6d}  {name}")
+    for arg in sys.argv[3:]:
+        if arg.startswith("--path="):
+            # a named path of basic blocks, e.g. --path=entry,.LBB17_3,.LBB17_40*1.4: the VALU of
+            # each listed block (times its trip count) summed per phase, i.e. the dynamic account of
+            # the wave that takes that path
+            by = {b[0]: b for b in blocks}
+            dyn, tot = collections.Counter(), collections.Counter()
+            for item in arg[len("--path="):].split(","):
+                label, _, cnt = item.partition("*")
+                n = float(cnt) if cnt else 1.0
+                _, c, lc = by[label]
+                for (p, _loc), v in lc.items():
+                    dyn[p] += v * n
+                for k in ("VALU", "SALU", "LDS", "VMEM"):
+                    tot[k] += c[k] * n
+            print(f"\n# path account (dynamic, per wave): VALU {tot['VALU']:.1f} SALU {tot['SALU']:.1f} "
+                  f"LDS {tot['LDS']:.1f} VMEM {tot['VMEM']:.1f}")
+            for _, name in tab:
+                if dyn[name]:
+                    print(f"{dyn[name]:8.1f}  {name}")
     if show_blocks:
         print("\n# basic blocks: label, VALU, SALU, LDS, VMEM, branch targets, then phase:file:line x count")
         for label, c, lc in blocks:
