@@ -114,6 +114,15 @@ namespace ptv {
 #ifndef PTV_FILTER_SEEDED
 #define PTV_FILTER_SEEDED 0  // dev builds: 1 = the filter's first gather pass at its wave's largest seed bound
 #endif
+#ifndef PTV_ROW_CHORD_FMA
+#define PTV_ROW_CHORD_FMA 1  // row phase: the sub-ball chord's r^2 - h^2 as one fma (0: the clamped sum)
+#endif
+#ifndef PTV_ROW_CHORD_MAX
+#define PTV_ROW_CHORD_MAX 1  // row phase: the widest chord per x-half, the interval's ends once per row
+#endif
+#ifndef PTV_ROW_INDEX_HALF
+#define PTV_ROW_INDEX_HALF 1  // row phase: row / nyr from (row + 0.5) * (1 / nyr), no correction pair
+#endif
 #ifndef PTV_STAMP_SEEDSPLIT
 #define PTV_STAMP_SEEDSPLIT 0  // dev stamp builds: union-seed counting passes stamped as 'setup'
 #endif
@@ -924,6 +933,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(knn_waves<K
     constexpr bool kTrimPair = !KEYS && !EXACT;
     // the IDW epilogue's in-range forms, same instantiations but eight-slot lists only
     constexpr bool kTrimEpi = kTrimPair && PTV_TRIM_EPI != 0 && KMAX == 8;
+    // row phase (round 12), each with the parent's form as its other branch
+    constexpr bool kRowChordFma = kTrimPair && PTV_ROW_CHORD_FMA != 0;   // sub-ball chord: r^2 - h^2 by one fma
+    constexpr bool kRowChordMax = kTrimPair && PTV_ROW_CHORD_MAX != 0;   // widest chord per x-half, ends once
+    constexpr bool kRowIndexHalf = kTrimPair && PTV_ROW_INDEX_HALF != 0; // row / nyr without the correction pair
     const int lb = (int)(blockIdx.y * gridDim.x + blockIdx.x);  // linear dispatch order
     if (lb >= a.nblocks) return;                                  // 2-D grid padding (block-uniform)
     if (a.gate != nullptr && !(__longlong_as_double((long long)*a.gate) <= a.gate_halo))
@@ -1859,10 +1872,25 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(knn_waves<K
                     rs[2 * q] = rs[2 * q + 1] = 0;
                     rc[2 * q] = rc[2 * q + 1] = 0;
                     if (row < nrows) {
-                        int rq = (int)((float)row * inv_nyr);  // row / nyr without an integer divide
-                        rq -= (rq * nyr > row) ? 1 : 0;
-                        rq += ((rq + 1) * nyr <= row) ? 1 : 0;
-                        const int ty = row - rq * nyr;
+                        int rq, ty;  // row / nyr without an integer divide, and the remainder
+                        if (kRowIndexHalf && nrows < (1 << 21)) {
+                            // (row + 0.5) / nyr is at least 0.5 / nyr away from every integer and, below
+                            // 2^21, exact in fp32; inv_nyr and the product are each within 2^-24
+                            // relative, so the error is under (2^21 / nyr) * 2^-23 = 0.25 / nyr and
+                            // the truncation is floor(row / nyr) exactly: no correction pair.  Both
+                            // factors of the remainder are below 2^21, so the 24-bit multiply holds it.
+                            // (a scalar branch on the uniform nrows; the empty asm keeps the compiler
+                            // from computing both forms on every lane and selecting)
+                            asm volatile("");
+                            rq = (int)(((float)row + 0.5f) * inv_nyr);
+                            ty = row - __mul24(rq, nyr);
+                        } else {
+                            if constexpr (kRowIndexHalf) asm volatile("");
+                            rq = (int)((float)row * inv_nyr);
+                            rq -= (rq * nyr > row) ? 1 : 0;
+                            rq += ((rq + 1) * nyr <= row) ? 1 : 0;
+                            ty = row - rq * nyr;
+                        }
                         const int ccy = cyc + ((ty & 1) ? ((ty + 1) >> 1) : -(ty >> 1));
                         const int ccz = czc + ((rq & 1) ? ((rq + 1) >> 1) : -(rq >> 1));
                         const double gy = axis_gap(ccy, g.o[1], g.cs[1], by0, by1);
@@ -1912,17 +1940,56 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(knn_waves<K
                                 const float zlo = (float)(g.o[2] + (double)ccz * g.cs[2] - tcz) - em;
                                 const float zhi = (float)(g.o[2] + (double)(ccz + 1) * g.cs[2] - tcz) + em;
                                 float xl = INFINITY, xh = -INFINITY;
+                                float hwm[2] = {-INFINITY, -INFINITY};  // widest chord per x-half (kRowChordMax)
+                                float h2cap = 0.f;                       // h2s of the x-half pair, capped (kRowChordFma)
 #pragma unroll
                                 for (int sb = 0; sb < 8; ++sb) {
                                     const float cyv = sby[(sb >> 1) & 1], czv = sbz[sb >> 2];
                                     const float gy = fmaxf(fmaxf(ylo - cyv, cyv - yhi), 0.f);
                                     const float gz = fmaxf(fmaxf(zlo - czv, czv - zhi), 0.f);
-                                    const float h2s = __fmaf_rn(gz, gz, gy * gy);
+                                    float h2s = __fmaf_rn(gz, gz, gy * gy);
+                                    // (the cap of the fma form below, on the four values of h2s a row has:
+                                    // the x-halves sb and sb ^ 1 share theirs.  It also enters the test,
+                                    // which then passes inf against the largest finite r2: wider, never
+                                    // narrower)
+                                    if constexpr (kRowChordFma) h2s = (sb & 1) ? h2cap : (h2cap = fminf(h2s, 3.402823466e+38f));
                                     if (h2s <= sbr2[sb]) {
-                                        const float hw = sqrtf_up(fmaxf(sbr2[sb] - h2s, 0.f) + sbr2[sb] * 1e-6f);
-                                        xl = fminf(xl, sbx[sb & 1] - hw);
-                                        xh = fmaxf(xh, sbx[sb & 1] + hw);
+                                        float hw2;
+                                        if constexpr (kRowChordFma) {
+                                            // one fma for the inflated r^2 - h^2.  For finite r2 the parent's
+                                            // argument is at most (r2 - h2s) + r2 * (1e-6 + 2.0001 u), u = 2^-24,
+                                            // after its three roundings, i.e. (r2 - h2s) + 1.12e-6 r2.  The
+                                            // constant rounds to 1 + 13 * 2^-23 >= 1 + 1.43e-6 and the fma rounds
+                                            // once: >= (r2 - h2s) + (1.43e-6 - u (1 + 1.6e-6)) r2 >= (r2 - h2s) +
+                                            // 1.37e-6 r2 > 0, never below the parent's (the clip only widens) and
+                                            // in no need of a clamp at 0; a product that overflows gives inf,
+                                            // wider still.  r2 = inf (an overflowed Rs^2, or a `wide` tile) must
+                                            // give inf as the parent's max(NaN, 0) + inf did, also where the
+                                            // gap's square overflowed too (inf <= inf passes the test above):
+                                            // inf - inf would be NaN, which sqrtf_up's fmaxf turns into 1e-30,
+                                            // a chord of no width.  So h2s enters capped at the largest finite
+                                            // float (above): inf * c - FLT_MAX = inf.  For finite r2 the cap
+                                            // changes nothing, h2s <= r2 being finite already.
+                                            hw2 = __fmaf_rn(sbr2[sb], 1.0000015f, -h2s);
+                                        } else {
+                                            hw2 = fmaxf(sbr2[sb] - h2s, 0.f) + sbr2[sb] * 1e-6f;
+                                        }
+                                        const float hw = sqrtf_up(hw2);
+                                        if constexpr (kRowChordMax) {
+                                            hwm[sb & 1] = fmaxf(hwm[sb & 1], hw);
+                                        } else {
+                                            xl = fminf(xl, sbx[sb & 1] - hw);
+                                            xh = fmaxf(xh, sbx[sb & 1] + hw);
+                                        }
                                     }
+                                }
+                                if constexpr (kRowChordMax) {
+                                    // the four sub-balls of an x-half share their centre, and rounding is
+                                    // monotone: min_i fl(c - hw_i) = fl(c - max_i hw_i), likewise the upper
+                                    // end, so xl and xh are the parent's bit for bit.  A half with no chord
+                                    // keeps -inf and gives +inf / -inf, the parent's empty interval.
+                                    xl = fminf(sbx[0] - hwm[0], sbx[1] - hwm[1]);
+                                    xh = fmaxf(sbx[0] + hwm[0], sbx[1] + hwm[1]);
                                 }
                                 if (xl <= xh) {
                                     const int s0 = clampi(floor((tcx + (double)(xl - em) - g.o[0]) * g.ic[0]), g.nc[0]);
