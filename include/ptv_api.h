@@ -1133,6 +1133,28 @@ int ptv_last_stats(ptv_ctx *ctx, ptv_stats *st);
  */
 int ptv_debug_stamps(ptv_ctx *ctx, int mode, double *out23);
 
+/*
+ * Diagnostics: per-wave XCD records of the stamped launch (ptv_debug_stamps mode 1 first):
+ * out receives up to cap records of 3 u64 {XCD the wave ran on, its first and its last value
+ * of the device's real-time clock (100 MHz)} in dispatch order (wave = block * 4 + wave of the
+ * block); *n_out = records copied.  Waves that wrote nothing have first == last == 0.
+ */
+int ptv_debug_xcd_stamps(ptv_ctx *ctx, unsigned long long *out, long long cap, long long *n_out);
+
+/*
+ * Diagnostics and tests: the chunk length, in blocks, of the map that deals the blocks of a k-NN
+ * launch without a dispatch order to the XCDs (chunks of consecutive blocks round-robin; results
+ * do not depend on it).  blocks > 0 sets it for every later launch of the process, 0 = one
+ * contiguous range per XCD, < 0 = back to the launcher's own choice.
+ */
+int ptv_debug_xcd_chunk(int blocks);
+
+/*
+ * That map on the host: out[lb] = the block that dispatch slot lb runs, lb in [0, nblocks).
+ * A bijection of [0, nblocks) for every chunk; slot lb runs on XCD lb % 8.
+ */
+int ptv_xcd_chunk_map(int nblocks, int chunk, int *out);
+
 #ifdef __cplusplus
 }
 #endif

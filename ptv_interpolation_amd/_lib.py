@@ -442,6 +442,9 @@ EXPORTS = {
                                     [C.c_void_p, C.POINTER(MgParams), C.POINTER(PressureStats), C.POINTER(MgStats)]),
     "ptv_last_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     "ptv_debug_stamps": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double)]),
+    "ptv_debug_xcd_stamps": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_longlong, C.POINTER(C.c_longlong)]),
+    "ptv_debug_xcd_chunk": (C.c_int, [C.c_int]),
+    "ptv_xcd_chunk_map": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int)]),
 }
 
 _lib = None
@@ -677,6 +680,20 @@ def device_count() -> int:
     return n.value
 
 
+def xcd_chunk_map(nblocks: int, chunk: int) -> np.ndarray:
+    """The block that each dispatch slot of a k-NN launch without a block order runs (host copy of
+    the kernel's map; slot lb runs on XCD lb % 8)."""
+    out = np.empty(int(nblocks), dtype=np.int32)
+    check(lib().ptv_xcd_chunk_map(int(nblocks), int(chunk), out.ctypes.data_as(C.POINTER(C.c_int))))
+    return out
+
+
+def debug_xcd_chunk(blocks: int) -> None:
+    """Chunk length of that map in blocks for every later launch (0: contiguous ranges, < 0: the
+    launcher's own choice).  Diagnostics and tests; results do not depend on it."""
+    check(lib().ptv_debug_xcd_chunk(int(blocks)))
+
+
 def as_dp(a: np.ndarray):
     return a.ctypes.data_as(_dp)
 
@@ -799,6 +816,14 @@ class Context:
                 "passes", "kept")
         v = list(out)
         return {"waves": v[0], "mean": dict(zip(keys, v[1:12])), "max": dict(zip(keys, v[12:23]))}
+
+    def debug_xcd_stamps(self, waves=1 << 21):
+        """(waves, 3) uint64 of the stamped launch, in dispatch order: XCD, first and last value of
+        the device's 100 MHz real-time clock; both 0 for a wave that wrote nothing."""
+        out = np.zeros((int(waves), 3), dtype=np.uint64)
+        n = C.c_longlong(0)
+        check(lib().ptv_debug_xcd_stamps(self.h, out.ctypes.data_as(C.POINTER(C.c_uint64)), int(waves), C.byref(n)))
+        return out[:n.value]
 
     # -- pore-mask path and outlier filter (SURVEY.md §8(f) rows 2-3) -------
     def sample_mask(self, raw, raw_axes, axes=None, grid_points=None, shape=None, z_range=None):

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "ptv_ctx.hpp"
+#include "ptv_xcd_map.hpp"
 
 namespace ptv {
 
@@ -628,17 +629,50 @@ int ptv_interp_linear(ptv_ctx *c, const ptv_particles *p, const ptv_grid *g, con
     return PTV_OK;
 }
 
+constexpr long long kStampCap = 1LL << 21;  // waves recorded
+constexpr int kXcdStampFields = 3;          // ptv_knn_impl.hpp: kStampXcdFields
+
+int ptv_debug_xcd_stamps(ptv_ctx *c, unsigned long long *out, long long cap, long long *n_out) {
+    if (!c || !out || !n_out || cap < 0) {
+        set_error("NULL argument");
+        return PTV_E_ARG;
+    }
+    *n_out = 0;
+    if (!c->dbg.p) return PTV_OK;
+    PTV_HIP(hipSetDevice(c->device));
+    PTV_HIP(hipDeviceSynchronize());
+    const long long n = std::min(cap, kStampCap);
+    PTV_HIP(hipMemcpy(out, c->dbg.p + (size_t)kStampCap * 8, (size_t)n * kXcdStampFields * sizeof(unsigned long long),
+                      hipMemcpyDeviceToHost));
+    *n_out = n;
+    return PTV_OK;
+}
+
+int ptv_debug_xcd_chunk(int blocks) {
+    ptv::g_xcd_chunk = blocks < 0 ? -1 : blocks;
+    return PTV_OK;
+}
+
+int ptv_xcd_chunk_map(int nblocks, int chunk, int *out) {
+    if (nblocks < 0 || (nblocks > 0 && !out)) {
+        set_error("ptv_xcd_chunk_map: bad arguments");
+        return PTV_E_ARG;
+    }
+    for (int lb = 0; lb < nblocks; ++lb) out[lb] = ptv::xcd_chunk_block(lb, nblocks, chunk);
+    return PTV_OK;
+}
+
 int ptv_debug_stamps(ptv_ctx *c, int mode, double *out) {
     if (!c) {
         set_error("NULL context");
         return PTV_E_ARG;
     }
     PTV_HIP(hipSetDevice(c->device));
-    constexpr long long cap = 1LL << 21;  // waves recorded (modulo-free: later waves dropped)
+    constexpr long long cap = kStampCap;  // modulo-free: later waves dropped
     constexpr int nf = 8;
-    if (mode == 1) {  // enable + zero
-        PTV_TRY(c->dbg.ensure((size_t)cap * nf));
-        PTV_HIP(hipMemsetAsync(c->dbg.p, 0, (size_t)cap * nf * sizeof(unsigned long long), c->stream));
+    if (mode == 1) {  // enable + zero: the phase records, then the plane of XCD records
+        PTV_TRY(c->dbg.ensure((size_t)cap * (nf + kXcdStampFields)));
+        PTV_HIP(hipMemsetAsync(c->dbg.p, 0, (size_t)cap * (nf + kXcdStampFields) * sizeof(unsigned long long), c->stream));
         PTV_HIP(hipStreamSynchronize(c->stream));
         ptv::g_dbg = c->dbg.p;
         ptv::g_dbg_cap = cap;

@@ -117,7 +117,7 @@ struct KnnLaunch {
     uint32_t *slots = nullptr;   // kModeSlots: (z1 - z0, ny, nx, k) neighbour slots out
     double radius = 0.0;         // kModeRadius: the search radius
     FilterEpilogue fe;           // kModeFilter
-    const int *order = nullptr;  // dispatch order of the launch's blocks (NULL: XCD-contiguous ranges)
+    const int *order = nullptr;  // dispatch order of the launch's blocks (NULL: the XCD chunk map)
     // near-tie repair of the packed-key lists (k >= 13, modes interp / slots / filter): a device
     // counter + tile list (rep_cap entries), a pinned host word for the count, and a counter of
     // repaired tiles (stats, may be NULL)
@@ -183,6 +183,7 @@ int launch_halo_need(const double *lax, const double *lay, const double *laz, in
 int kmax_for(int k);  // compile-time list length serving k, 0 if unsupported
 extern unsigned long long *g_dbg;  // per-wave phase stamps (diagnostics), NULL = off
 extern long long g_dbg_cap;
+extern int g_xcd_chunk;  // ptv_debug_xcd_chunk: blocks per chunk of the XCD map (< 0: launch_knn's choice)
 
 int launch_knn(const KnnLaunch &a, const Binned &b, const double *ax, const double *ay, const double *az,
                const double *qx, const double *qy, const double *qz, const uint8_t *mask, double *U, double *V,

@@ -6,6 +6,7 @@ namespace ptv {
 
 unsigned long long *g_dbg = nullptr;
 long long g_dbg_cap = 0;  // records
+int g_xcd_chunk = -1;
 
 // ---------------------------------------------------------------------------
 // Count-only k-th distance UPPER bound (coarsest lattice).  One wave per grid point;
@@ -338,6 +339,12 @@ static int launch_kmax(int km, bool exact, dim3 grid, hipStream_t s, const KnnKe
     return PTV_OK;
 }
 
+#ifndef PTV_XCD_CHUNK_PLANES
+#define PTV_XCD_CHUNK_PLANES 1
+#endif
+// tile planes (ntxb * nty blocks each) per chunk of the XCD map
+constexpr int kXcdChunkPlanes = PTV_XCD_CHUNK_PLANES;
+
 static dim3 grid_for(long long nblocks) {
     // a dispatch holds < 2^32 work-items per dimension: above 2^23 blocks of 256 the grid is
     // 2-D, x a multiple of 8 so that the linear order still deals blocks round-robin over XCDs
@@ -417,6 +424,13 @@ int launch_knn(const KnnLaunch &a, const Binned &b, const double *ax, const doub
         return PTV_E_ARG;
     }
     ka.nblocks = (int)nblocks;
+    // launches without a block order: chunks of whole tile planes dealt round-robin to the XCDs
+    // (ptv_xcd_map.hpp; one contiguous range per XCD where the grid has fewer than 16 chunks)
+    long long chunk = (long long)kXcdChunkPlanes * ka.ntxb * ka.nty;
+    if (g_xcd_chunk >= 0) chunk = g_xcd_chunk;
+    if (const char *e = dev_knob("PTV_XCD_PLANES")) chunk = std::atoll(e) * ka.ntxb * ka.nty;  // dev knobs: tile planes,
+    if (const char *e = dev_knob("PTV_XCD_CHUNK")) chunk = std::atoll(e);                      // blocks (0 = contiguous)
+    ka.xcd_chunk = (int)std::max(0LL, std::min(chunk, nblocks));
     // packed keys: slot bits B (the largest slot is n - 1) and the key -> d2 bound factor
     int B = 1;
     while (B < 31 && (1LL << B) < b.n) ++B;

@@ -44,6 +44,7 @@
 #include "ptv_kernels.hpp"
 #include "ptv_median.hpp"
 #include "ptv_wave.hpp"
+#include "ptv_xcd_map.hpp"
 
 namespace ptv {
 
@@ -131,6 +132,10 @@ namespace ptv {
 #endif
 
 constexpr int kStampFields = 8;
+// after the g_dbg_cap phase records, a second plane of kStampXcdFields u64 per wave: the XCD the wave
+// ran on (HW_REG_XCC_ID) and its first and last real-time clock values (s_memrealtime, 100 MHz, one
+// clock for the whole device; s_memtime is per XCD)
+constexpr int kStampXcdFields = 3;
 #ifndef PTV_TIGHTEN_MIN
 #define PTV_TIGHTEN_MIN 32
 #endif
@@ -163,7 +168,8 @@ constexpr int kRowsPerLane = 1;  // cell rows examined per lane per gather round
 constexpr int kRunEntries = 64 * 2 * kRowsPerLane;  // x-runs per gather round (power of two)
 
 // Diagnostics (ptv_debug_stamps): when set, KMAX=8 launches use the STAMP instantiation,
-// which writes one record of kStampFields u64 per wave (s_memtime phase cycles + counts).
+// which writes one record of kStampFields u64 per wave (s_memtime phase cycles + counts) and one of
+// kStampXcdFields (XCD, first and last real-time clock).
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
@@ -185,7 +191,8 @@ struct KnnKernelArgs {
     int nblocks;       // workgroups of the launch (the grid may be 2-D, see launch_knn)
     double radius;     // kModeRadius: every particle with d2 <= radius^2 (query_ball_point's test)
     FilterEpilogue fe;  // kModeFilter
-    const int *order;  // block dispatch order (NULL: XCD-contiguous ranges)
+    const int *order;  // block dispatch order (NULL: the XCD chunk map, ptv_xcd_map.hpp)
+    int xcd_chunk;     // blocks per chunk of that map (0: one contiguous range per XCD)
     // packed-key lists (KMAX >= 16, see insert_key): slot bits of a key, and the factor that
     // turns a key into an upper bound on its exact d2 (1 + 2^(B - 51), B = slot bits)
     uint32_t smask;
@@ -786,13 +793,6 @@ __device__ __forceinline__ double sqrt_up(double x) {
     return (double)sqrtf_up((float)(x * (1.0 + 2.384185791015625e-07)));
 }
 
-// bijection of [0, nb): block b (dispatched to XCD b % 8) -> a contiguous range per XCD
-__device__ __forceinline__ int xcd_block(int b, int nb) {
-    const int q = nb >> 3, r = nb & 7;
-    const int x = b & 7, i = b >> 3;
-    return (x < r) ? x * (q + 1) + i : r * (q + 1) + (x - r) * q + i;
-}
-
 // distance between the extent [lo, hi] of a query box and cell c of an axis
 __device__ __forceinline__ double axis_gap(int c, double o, double cs, double lo, double hi) {
     const double c0 = o + (double)c * cs;
@@ -901,7 +901,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(knn_waves<K
             t_mark = t;
         }
     };
-    if constexpr (STAMP) t_mark = __builtin_amdgcn_s_memtime();
+    unsigned long long rt_first = 0;
+    unsigned int xcc = 0;
+    if constexpr (STAMP) {
+        rt_first = __builtin_amdgcn_s_memrealtime();
+        xcc = __builtin_amdgcn_s_getreg(20 | (3 << 11));  // hwreg(HW_REG_XCC_ID, 0, 4)
+        t_mark = __builtin_amdgcn_s_memtime();
+    }
     constexpr int kCap = cand_cap<KMAX>();
     __shared__ double4 lds_cand[4][kCap];
     __shared__ __attribute__((aligned(16))) float lds_cfx[4][kCap], lds_cfy[4][kCap], lds_cfz[4][kCap];
@@ -923,9 +929,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(knn_waves<K
     float *fbx = lds_cfx[wid], *fby = lds_cfy[wid], *fbz = lds_cfz[wid];
     uint2 *runs = lds_runs[wid];
     int *owner = lds_owner[wid];
-    // XCD-aware block order: the dispatcher deals workgroups round-robin over the 8 XCDs,
-    // so give XCD x a contiguous range of tiles (neighbouring tiles share cell rows and
-    // particle records; each XCD has its own L2)
+    // XCD-aware block order: the dispatcher deals workgroups round-robin over the 8 XCDs, so
+    // give XCD x chunks of consecutive tiles (neighbouring tiles share cell rows and particle
+    // records; each XCD has its own L2), interleaved with the other XCDs' over the whole grid
     constexpr bool KEYS = kKeyList<KMAX, EXACT>;
     // the trimmed prefilter mask, copy-window test and row setup (below) are compiled for the pair
     // lists of the search proper only (k <= 12): in some key-list and exact-repair instantiations
@@ -962,7 +968,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(knn_waves<K
         b = (int)(t >> 2);
         tw = (int)(t & 3u);
     } else {
-        b = a.order != nullptr ? a.order[lb + a.order_skip] : xcd_block(lb, a.nblocks);
+        b = a.order != nullptr ? a.order[lb + a.order_skip] : xcd_chunk_block(lb, a.nblocks, a.xcd_chunk);
         tw = wid;
     }
     b = __builtin_amdgcn_readfirstlane(b);  // wave-uniform (the tile list is read per wave)
@@ -2173,6 +2179,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(knn_waves<K
                 r[5] = t_epi;
                 r[6] = n_cand + ((unsigned long long)n_acc << 32);
                 r[7] = (n_round & 0xffffu) + ((unsigned long long)(n_pass & 0xffffu) << 16) + ((unsigned long long)n_surv << 32);
+                unsigned long long *x = dbg + dbg_cap * kStampFields + gw * kStampXcdFields;
+                x[0] = xcc;
+                x[1] = rt_first;
+                x[2] = __builtin_amdgcn_s_memrealtime();
             }
         }
     };
