@@ -556,12 +556,13 @@ def _faces(vel, fluid, axis):
     f_prev[i] = f_next[i-1] = (vel[i-1] + vel[i]) / 2 if fluid[i] else 0, = vel[i] at i = 0."""
     v = np.moveaxis(vel, axis, -1)
     m = np.moveaxis(fluid, axis, -1)
-    zero = np.zeros((), dtype=vel.dtype)
-    fn = np.empty_like(v)
-    fp = np.empty_like(v)
-    fn[..., :-1] = np.where(m[..., 1:], (v[..., :-1] + v[..., 1:]) / 2.0, zero)
+    avg = (v[..., :-1] + v[..., 1:]) / 2.0  # the field's dtype; float64 for an integer field
+    zero = np.zeros((), dtype=avg.dtype)
+    fn = np.empty(v.shape, dtype=avg.dtype)
+    fp = np.empty(v.shape, dtype=avg.dtype)
+    fn[..., :-1] = np.where(m[..., 1:], avg, zero)
     fn[..., -1] = v[..., -1]
-    fp[..., 1:] = np.where(m[..., 1:], (v[..., :-1] + v[..., 1:]) / 2.0, zero)
+    fp[..., 1:] = np.where(m[..., 1:], avg, zero)
     fp[..., 0] = v[..., 0]
     return np.moveaxis(fn, -1, axis), np.moveaxis(fp, -1, axis)
 
