@@ -25,10 +25,16 @@
 // that short is summed whole, with scipy's z^n terms.  The recursion's state is a double-double and
 // the array holds its rounding: between two passes a coefficient is rounded once.
 //
-// Sampling.  One lane per point.  Order 3 reads the padded coefficients at coordinate + 12, clamped
-// to the padded extent only (scipy samples the padded array: the spline's own extrapolation over
-// the replicated edge, not the value at the clamped coordinate).  The 4 x 4 x 4 block is summed
-// separably, x innermost: 16 row sums, 4 plane sums, one value, weights and sums in double-double.
+// Sampling.  One lane per point.  Order 3 reads the padded coefficients at coordinate + 12 (scipy
+// samples the padded array: the spline's own extrapolation over the replicated edge, not the value
+// at the clamped coordinate).  The coordinate is clamped one sample past the padded extent, to
+// [-1, N] of the padded index space, and the four indices to [0, N - 1], as scipy does: past the pad
+// the fraction still moves the weights over the edge-extended coefficients until the value saturates
+// at -1 and at N (cell_of).  The 4 x 4 x 4 block is summed separably, x innermost: 16 row sums, 4
+// plane sums, one value, weights and sums in double-double.  Order 1 reads the raw field at the
+// coordinate clamped to [0, n - 1].  A non-finite order-1 sample takes its kind (NaN, +Inf, -Inf)
+// from the plain float64 sum, since the double-double error terms turn every Inf into NaN; order 3
+// over a non-finite coefficient is NaN.
 //
 // Traction integration.  One lane per triangle, blocks of 256 that never span two labels (the host
 // builds the block -> (label, first triangle) table).  A block reduces the 21 terms in a fixed
@@ -251,17 +257,22 @@ __device__ __forceinline__ double clampc(double c, double hi) {
 }
 
 // Where a coordinate a + b of the raw field's index space falls in an array of extent N that
-// starts `pad` samples before it: the index of floor and the fraction, clamped to the array.  The
-// fraction is (a - floor) + b as a double-double, so the rounding of a + b (at the magnitude of the
-// coordinate) does not enter the weights; a - floor is exact for a float32-born a.  NaN gives 0.
+// starts `pad` samples before it: the index of floor and the fraction, clamped to [-over, N - 1 +
+// over] in the array's own index space.  Order 1 samples the raw field with over = 0: the cell is an
+// index.  Order 3 samples the padded coefficients with over = 1, which is scipy's rule: one sample
+// past either end the fraction is kept and only the four indices are edge-extended (cubic_axis), at
+// -1 and at N the value saturates, and any coordinate beyond (however large) gives that same cell.
+// The fraction is (a - floor) + b as a double-double, so the rounding of a + b (at the magnitude of
+// the coordinate) does not enter the weights; a - floor is exact for a float32-born a.  NaN gives
+// the low end.
 struct Cell {
     int64_t i;
     dd t;
 };
-__device__ __forceinline__ Cell cell_of(double a, double b, int pad, int64_t N) {
+__device__ __forceinline__ Cell cell_of(double a, double b, int pad, int64_t N, int over) {
     const double c = a + b;
-    if (!(c > -(double)pad)) return Cell{0, dd{0.0, 0.0}};
-    if (c >= (double)(N - 1 - pad)) return Cell{N - 1, dd{0.0, 0.0}};
+    if (!(c > -(double)(pad + over))) return Cell{-(int64_t)over, dd{0.0, 0.0}};
+    if (c >= (double)(N - 1 - pad + over)) return Cell{N - 1 + over, dd{0.0, 0.0}};
     const double f = floor(c);
     return Cell{(int64_t)f + pad, two_sum(a - f, b)};
 }
@@ -327,7 +338,18 @@ __device__ __forceinline__ dd sample1(const T *__restrict__ F, int nz, int ny, i
         }
         sz = dd_add(sz, dd_mul(kz ? c[0].t : w0[0], sy));
     }
-    return sz;
+    if (sz.hi - sz.hi == 0.0) return sz;
+    // A non-finite sample among the eight: the products' error terms are Inf - Inf, so the sum above is
+    // NaN whatever the kind.  scipy's plain sum, corner by corner, keeps +-Inf under a positive weight
+    // and gives NaN under a zero one; its kind is the result's.
+    double plain = 0.0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const int kz = k >> 2, ky = (k >> 1) & 1, kx = k & 1;
+        const double v = (double)F[((kz ? i1[0] : c[0].i) * ny + (ky ? i1[1] : c[1].i)) * nx + (kx ? i1[2] : c[2].i)];
+        plain += ((v * (kz ? c[0].t.hi : w0[0].hi)) * (ky ? c[1].t.hi : w0[1].hi)) * (kx ? c[2].t.hi : w0[2].hi);
+    }
+    return dd{plain, 0.0};
 }
 
 // order 0: the linear index of the sample at floor(c + 0.5), clamped
@@ -350,10 +372,11 @@ __global__ __launch_bounds__(kLineThreads) void k_map_coordinates(SplineDims d, 
         const int64_t N[3] = {d.pz(), d.py(), d.px()};
         Cubic q;
 #pragma unroll
-        for (int a = 0; a < 3; ++a) cubic_axis(q, a, cell_of(co[a], 0.0, kPad, N[a]), N[a]);
+        for (int a = 0; a < 3; ++a) cubic_axis(q, a, cell_of(co[a], 0.0, kPad, N[a], 1), N[a]);
         out[i] = bad ? nan("") : sample3((const double *)src, N[1], N[2], q).hi;
     } else if constexpr (ORDER == 1) {
-        const Cell c[3] = {cell_of(co[0], 0.0, 0, d.nz), cell_of(co[1], 0.0, 0, d.ny), cell_of(co[2], 0.0, 0, d.nx)};
+        const Cell c[3] = {cell_of(co[0], 0.0, 0, d.nz, 0), cell_of(co[1], 0.0, 0, d.ny, 0),
+                           cell_of(co[2], 0.0, 0, d.nx, 0)};
         out[i] = bad ? nan("") : sample1<T>(src, d.nz, d.ny, d.nx, c).hi;
     } else {
         out[i] = (double)src[index0(d.nz, d.ny, d.nx, co[0], co[1], co[2])];
@@ -421,8 +444,8 @@ __global__ __launch_bounds__(kMeshThreads) void k_mesh_terms(
         Cell at[3];
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            cubic_axis(q, c, cell_of(cen[c], off[c], kPad, N[c]), N[c]);  // the offset sample: centroid + 0.25 n
-            at[c] = cell_of(cen[c], 0.0, 0, n3[c]);                      // the centroid
+            cubic_axis(q, c, cell_of(cen[c], off[c], kPad, N[c], 1), N[c]);  // the offset sample: centroid + 0.25 n
+            at[c] = cell_of(cen[c], 0.0, 0, n3[c], 0);                      // the centroid
         }
         const T *fld[3] = {U, V, W};
         const double *cf[3] = {CU, CV, CW};

@@ -9,6 +9,17 @@ edge-replicated samples on every side, ``spline_filter(np.pad(input, 12, mode='e
 mode='nearest')``.  float32 input is widened exactly, integer and bool input is computed as
 float64.  Anything else raises ``NotImplementedError``; there is no CPU fallback.
 
+Coordinates outside the field follow scipy for any finite value it defines.  Orders 0 and 1 clamp
+the coordinate to ``[0, n - 1]``.  Order 3 samples the padded coefficients at the padded coordinate
+clamped to ``[-1, n + 24]``, one sample past either end, with the four indices edge-extended: up to
+13 samples outside the field the value still moves, from there on it is saturated.  Beyond 2^62 in
+magnitude scipy is undefined (its integer cast overflows; from 1e19 it returns garbage); here such
+a coordinate gives the saturated value, the same as at 1e6.
+
+Non-finite field values.  Orders 0 and 1 return NaN and +-Inf exactly where scipy does.  At order 3
+one non-finite sample makes every coefficient non-finite, in scipy too; scipy's are NaN or Inf and
+the double-double recursion here turns Inf into NaN, so the results agree in finiteness, not in kind.
+
 An order-3 call filters the whole field.  To sample one field several times, filter it once:
 ``map_coordinates(None, coordinates, shape=input.shape)`` samples the coefficients the last
 order-3 call left in the context.

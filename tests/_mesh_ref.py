@@ -96,12 +96,17 @@ def prefilter(field, ft=LD):
 
 
 def sample3(coef, coords):
-    """Order 3 on the padded coefficients at coords (3, n) of the raw field's index space."""
+    """Order 3 on the padded coefficients at coords (3, n) of the raw field's index space.
+
+    scipy's rule past the pad (probed in tests/test_spline_edge_cases.py): the padded coordinate is
+    clamped to [-1, N], one sample past either end of the padded extent N, not to [0, N - 1]; the
+    fraction is kept there and only the four indices are edge-extended, so the value still moves
+    between -1 and 0 and between N - 1 and N and saturates at -1 and at N."""
     ft = coef.dtype.type
     total = np.zeros(coords.shape[1], dtype=ft)
     wts, idx = [], []
     for a in range(3):
-        c = np.clip(coords[a].astype(ft) + PAD, 0, coef.shape[a] - 1)
+        c = np.clip(coords[a].astype(ft) + PAD, -1, coef.shape[a])
         f = np.floor(c)
         t = c - f
         wts.append([(1 - t) ** 3 / 6, (3 * t ** 3 - 6 * t ** 2 + 4) / 6, (-3 * t ** 3 + 3 * t ** 2 + 3 * t + 1) / 6,
